@@ -44,7 +44,29 @@ def parse():
                     help="BASELINE.json config: 2 = DGEMM 8192^3 N=14 INT8 (headline, default); 3 = SGEMM 16384^3 N=6 FP8; "
                          "4 = DGEMM 16384^3 N=16 INT8 (same code path as 2 at that size; meant for --gpus 8 under torch.distributed.run); "
                          "5 = ZGEMM 8192^3 N=20 INT8 (single GPU only; extra measurement lines, not the driver's metric)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the C of the last timed step to DIR/C.npy (see dump_outputs) for output-for-output comparisons")
     return ap.parse_args()
+
+
+DUMP_VALUES = 1 << 22   # per dumped array: 4 Mi float64 values = 32 MB
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> column-major matrix held as a (cols, rows) tensor) as DIR/<name>.npy, float32 or
+    float64, complex values as a trailing (re, im) axis.  Up to DUMP_VALUES values: the whole m x n matrix.  Larger: a fixed sample of
+    DUMP_VALUES / (1 or 2) elements, 1-D, at the sorted distinct flat column-major positions np.unique(default_rng(0).integers(0, m*n, count))
+    -- the same positions in every run of the same shape."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        per = 2 if t.is_complex() else 1
+        if t.numel() * per <= DUMP_VALUES:
+            t = t.transpose(0, 1)   # (rows, cols)
+        else:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_VALUES // per))
+            print(f"[bench] {name}.npy: {idx.size} of {t.numel()} elements, at seeded column-major positions", file=sys.stderr)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), (torch.view_as_real(t) if t.is_complex() else t).cpu().numpy())
 
 
 def make_inputs(n, device):
@@ -152,6 +174,7 @@ def run_other_config(args):
         e1.record()
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1))
+    C_timed = Cm.clone() if args.dump_outputs else None   # the comparison calls below overwrite Cm
     _, tm, _ = g.gemm(A, B, N, fastmode=mode, backend=be, C_out=Cm, work=work, timers=True)
     ms = float(np.median(ts))
     rows = np.arange(0, n, n // 32)[:32]
@@ -255,6 +278,8 @@ def run_other_config(args):
                                  "elements_of_C_that_differ": int((C0 != Cm).sum().item()), "elements": n * n,
                                  "max_rel_diff_of_C_between_modes": float(((C0 - Cm).abs() / C0.abs().clamp_min(1e-30)).max().item())}
         del C0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"C": C_timed})
     print(json.dumps(out))
 
 
@@ -581,6 +606,8 @@ def run_plans(args, n, N, A, B, dev, stream, backend, rank, world):
         results["fp64sum"]["elements"] = int(ref.numel())
         exact = [k_ for k_ in ("blocks", "moduli") if results[k_]["mismatches_vs_moduli"] == 0]
         headline = max(exact, key=lambda k_: results[k_]["value"])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"C": gathered[headline]})
     comm.close()
     return results, headline, info
 
@@ -799,6 +826,8 @@ def main():
     out["phase_ms"] = {"bounds": float(np.mean([e[4].elapsed_time(e[0]) for e in phase_events])) if not args.fast else 0.0,
                        "quantise": q_ms, "lowprec_gemm": gemm_ms, "crt": c_ms}
     out["max_rel_err"] = sampled_error(A, B, C_head, n)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"C": C_head})
     nat["max_rel_err"] = sampled_error(A, B, Cn, n)
     del Cn, C_head
     out["native_fp64_dgemm_same_gpu"] = nat

@@ -61,3 +61,29 @@ def test_roofline_traffic_comes_from_the_manifest():
     assert got and got["source"] == "profiles/" + ent["pmc_traffic"] and got["kernel"] == ent["kernel"]
     assert 2.82e9 < got["hbm_side_bytes_per_launch"] < 40e9      # above the algorithmic 2.82 GB, far below a re-read of everything per tile row
     assert bench.traffic_manifest_entry(4096, 14) is None and bench.traffic_manifest_entry(8192, 15) is None
+
+
+def test_dump_outputs_writes_whole_or_seeded_sample(tmp_path):
+    """--dump-outputs: a small C whole in (rows, cols) order, a large one as the same seeded sample in every run, complex as (re, im) pairs,
+    float32 / float64 kept, and never more than 32 MB per array."""
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test3", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 2100                                                     # 4.4 Mi elements: above the whole-matrix limit
+    C = torch.arange(n * n, dtype=torch.float64).reshape(n, n)   # (cols, rows) of a column-major matrix: value = flat position
+    Z = torch.complex(C[:1500, :1500], -C[:1500, :1500]).contiguous()
+    S = torch.arange(64 * 48, dtype=torch.float32).reshape(48, 64)
+    runs = []
+    for r in range(2):
+        d = str(tmp_path / str(r))
+        bench.dump_outputs(d, {"C": C, "Z": Z, "S": S})
+        runs.append({k: np.load(os.path.join(d, k + ".npy")) for k in ("C", "Z", "S")})
+        assert all(os.path.getsize(os.path.join(d, k + ".npy")) <= 32 * 2 ** 20 + 256 for k in ("C", "Z", "S"))
+    for k in ("C", "Z", "S"):
+        assert np.array_equal(runs[0][k], runs[1][k])
+    s, c, z = runs[0]["S"], runs[0]["C"], runs[0]["Z"]
+    assert s.dtype == np.float32 and s.shape == (64, 48) and s[1, 0] == 1 and s[0, 1] == 64
+    assert c.dtype == np.float64 and np.array_equal(c, np.unique(np.random.default_rng(0).integers(0, n * n, 2 ** 22)))
+    assert z.shape[1] == 2 and z.shape[0] <= 2 ** 21 and np.array_equal(z[:, 1], -z[:, 0])

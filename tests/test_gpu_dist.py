@@ -275,11 +275,12 @@ def _one_json_line(out):
     return json.loads(lines[0])
 
 
-@pytest.mark.parametrize("ranks", [2, 8])
+@pytest.mark.parametrize("ranks", [2, 4])
 def test_bench_multi_rank_contract(ranks):
-    """bench.py as the driver launches it for N > 1 (torch.distributed.run, one rank per process), here with 2 or 8 ranks sharing
+    """bench.py as the driver launches it for N > 1 (torch.distributed.run, one rank per process), here with 2 or 4 ranks sharing
     the box's single GPU over gloo (GEMMUL8_DIST_BACKEND: NCCL refuses duplicate devices): ONE JSON line from rank 0 with the
-    contract keys, the right rank count, all three plans measured, an accurate result."""
+    contract keys, the right rank count, all three plans measured, an accurate result.  4 ranks, not 8: with this process and the
+    launcher that already puts 6 processes on the one GPU of a shared test machine, the most it takes at once."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
