@@ -34,7 +34,7 @@ class Layout(C.Structure):
 _lib = None
 
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
-           "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode",
+           "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
            "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
@@ -120,6 +120,8 @@ def bind(L):
                                        C.c_void_p, C.c_size_t, C.c_longlong, C.c_size_t, C.c_uint, C.c_int, C.c_void_p]
     L.gemmul8_set_fp8_bound_mode.restype = C.c_int
     L.gemmul8_set_fp8_bound_mode.argtypes = [C.c_int]
+    L.gemmul8_set_nonfinite_mode.restype = C.c_int
+    L.gemmul8_set_nonfinite_mode.argtypes = [C.c_int]
     L.gemmul8_hook_would_emulate.restype = C.c_int
     L.gemmul8_hook_would_emulate.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint, C.c_int, C.c_size_t]
     L.gemmul8_reload_knobs.restype = None
@@ -129,6 +131,18 @@ def bind(L):
     L.gemmul8_add_row_bias.restype = C.c_int
     L.gemmul8_add_row_bias.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     return L
+
+
+NONFINITE_REFERENCE, NONFINITE_IEEE = 0, 1
+
+
+def set_nonfinite_mode(mode):
+    """Process-wide handling of NaN / Inf operands in gemm / gemm_batched (include/gemmul8_c.h, gemmul8_set_nonfinite_mode): 0 = the
+    default (operands assumed finite), 1 = BLAS-like propagation ("ieee").  Returns the previous mode; anything else raises ValueError."""
+    prev = lib().gemmul8_set_nonfinite_mode(int(mode))
+    if prev < 0:
+        raise ValueError(f"non-finite mode {mode!r}: 0 or 1")
+    return prev
 
 
 def work_size(is_complex, backend, m, n, k, num_moduli, enA=False, enB=False):

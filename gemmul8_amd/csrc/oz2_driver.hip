@@ -125,6 +125,13 @@ extern "C" {
 
 void gemmul8_reload_knobs(void) { oz2::reload_knobs(); }
 
+// non-finite mode (include/gemmul8_c.h): read once per whole call by gemmul8_gemm / gemmul8_gemm_batched
+static std::atomic<int> g_nonfinite_mode{0};
+int gemmul8_set_nonfinite_mode(int mode) {
+    if (mode < 0 || mode > 1) return GEMMUL8_E_ARG;
+    return g_nonfinite_mode.exchange(mode);
+}
+
 int gemmul8_set_fp8_bound_mode(int mode) {
     if (mode < 0 || mode > 2) return GEMMUL8_E_ARG;
     const int old = get_f8_bound_mode();
@@ -221,9 +228,10 @@ static int scale_scratch(const gemmul8_layout* L, size_t n, int** rowmax, int** 
     return GEMMUL8_OK;
 }
 
-int gemmul8_scale_bounds(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A,
-                         size_t lda, const void* B, size_t ldb, unsigned N, size_t col_begin, size_t col_end, const gemmul8_layout* L,
-                         int skipA, int skipB) {
+// nf: non-finite mode 1 (gemmul8_set_nonfinite_mode) -- passed down from the whole-call entry points only; the phase-level entry points run mode 0
+static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
+                           const void* B, size_t ldb, unsigned N, size_t col_begin, size_t col_end, const gemmul8_layout* L, int skipA, int skipB,
+                           bool nf) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!L || !A || !B) return GEMMUL8_E_ARG;
     if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
@@ -267,6 +275,12 @@ int gemmul8_scale_bounds(void* stream_, int dtype, int backend, int op_A, int op
         OZ2_HIP(launch_extract_pair(stream, dtype, backend, k, L->kp, ea, ExtractOperand{}, nullptr, 0));
         OZ2_HIP(launch_extract_pair(stream, dtype, backend, k, L->kp, ExtractOperand{}, eb, nullptr, 0));
     }
+    if (nf) {  // flagged rows / columns: sentinel shifts and zero bound planes before the bound GEMM reads them
+        FlagOperand fa, fb;
+        if (runA) fa = FlagOperand{kmajA, m, A, lda, g_batch.sa, L->sftA, s0A, (int8_t*)L->A_bound, L->kp, L->parts, bstrideA};
+        if (runB) fb = FlagOperand{kmajB, n, B, ldb, g_batch.sb, L->sftB, s0B, (int8_t*)L->B_bound, L->kp, L->parts, bstrideB};
+        OZ2_HIP(launch_flag_pair(stream, dtype, k, fa, fb));
+    }
     if (col_end > col_begin) {
         const int8_t* Ab = (const int8_t*)L->A_bound;
         const int8_t* Bb = (const int8_t*)L->B_bound + col_begin * L->kp;
@@ -307,9 +321,15 @@ int gemmul8_scale_bounds(void* stream_, int dtype, int backend, int op_A, int op
     return GEMMUL8_OK;
 }
 
-int gemmul8_scale_finish(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A,
-                         size_t lda, const void* B, size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end,
-                         const gemmul8_layout* L, int skipA, int skipB) {
+int gemmul8_scale_bounds(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A,
+                         size_t lda, const void* B, size_t ldb, unsigned N, size_t col_begin, size_t col_end, const gemmul8_layout* L,
+                         int skipA, int skipB) {
+    return scale_bounds_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, col_begin, col_end, L, skipA, skipB, false);
+}
+
+static int scale_finish_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
+                           const void* B, size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end, const gemmul8_layout* L, int skipA,
+                           int skipB, bool nf) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!L || !A || !B) return GEMMUL8_E_ARG;
     if (!moduli_ok(dtype, N) || t_end > N || t_begin > t_end) return GEMMUL8_E_NUM_MODULI;
@@ -325,8 +345,15 @@ int gemmul8_scale_finish(void* stream_, int dtype, int backend, int op_A, int op
     const bool f6 = backend == kFP8 && L->lo_format == 1;  // FP6 panel images (oz2_gemm_f6.hip): A's blocks are whole (mp rows), B's last one may be short
     if (!skipA) oa = QuantOperand{kmajA, conjA, m, A, lda, L->sftA, (int8_t*)L->A_lo, L->sizeA, L->part_strideA, g_batch.sa, f6 ? L->mp : 0};
     if (!skipB) ob = QuantOperand{kmajB, conjB, n, B, ldb, L->sftB, (int8_t*)L->B_lo, L->sizeB, L->part_strideB, g_batch.sb, f6 ? n : 0};
+    oa.nf = ob.nf = nf;
     if (fastmode) {
         OZ2_HIP(launch_fast_shift_pair(stream, dtype, backend, N, k, oa, ob));
+        if (nf) {  // flagged rows / columns: sentinel shifts before the quantise reads them
+            FlagOperand fa, fb;
+            if (!skipA) fa = FlagOperand{kmajA, m, A, lda, g_batch.sa, L->sftA};
+            if (!skipB) fb = FlagOperand{kmajB, n, B, ldb, g_batch.sb, L->sftB};
+            OZ2_HIP(launch_flag_pair(stream, dtype, k, fa, fb));
+        }
     } else {
         int *rowmax, *colmax;
         void* amax;
@@ -340,21 +367,32 @@ int gemmul8_scale_finish(void* stream_, int dtype, int backend, int op_A, int op
             oa.fin_sft0 = s0A, oa.fin_max = rowmax, oa.fin_log2P = log2P;
             ob.fin_sft0 = s0B, ob.fin_max = colmax, ob.fin_log2P = log2P;
         } else {  // no plane to write (a rank without moduli): the shifts are still wanted by the CRT
-            OZ2_HIP(launch_shift_finalize(stream, backend, N, skipA ? 0 : m, rowmax, L->sftA, skipB ? 0 : n, colmax, L->sftB));
+            OZ2_HIP(launch_shift_finalize(stream, backend, N, skipA ? 0 : m, rowmax, L->sftA, skipB ? 0 : n, colmax, L->sftB, nf));
         }
     }
     OZ2_HIP(launch_quantise_pair(stream, dtype, backend, (int)t_begin, (int)t_end, k, L->kp, oa, ob));
     return GEMMUL8_OK;
 }
 
+int gemmul8_scale_finish(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A,
+                         size_t lda, const void* B, size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end,
+                         const gemmul8_layout* L, int skipA, int skipB) {
+    return scale_finish_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB, false);
+}
+
+static int scale_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda, const void* B,
+                    size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end, const gemmul8_layout* L, int skipA, int skipB, bool nf) {
+    if (!fastmode) {
+        int rc = scale_bounds_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, 0, n, L, skipA, skipB, nf);
+        if (rc) return rc;
+    }
+    return scale_finish_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB, nf);
+}
+
 int gemmul8_scale(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
                   const void* B, size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end, const gemmul8_layout* L,
                   int skipA, int skipB) {
-    if (!fastmode) {
-        int rc = gemmul8_scale_bounds(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, 0, n, L, skipA, skipB);
-        if (rc) return rc;
-    }
-    return gemmul8_scale_finish(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB);
+    return scale_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB, false);
 }
 
 int gemmul8_lowprec_gemm(void* stream_, int dtype, int backend, size_t m, size_t n, size_t k, unsigned N, unsigned t_begin,
@@ -563,7 +601,8 @@ int gemmul8_gemm(void* stream_, int dtype, int backend, int op_A, int op_B, size
         (void)hipGetLastError();
         T = nullptr;
     }
-    rc = gemmul8_scale(stream, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, 0, N, &L, skipA, skipB);
+    const bool nf = g_nonfinite_mode.load(std::memory_order_relaxed) == 1;
+    rc = scale_nf(stream, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, 0, N, &L, skipA, skipB, nf);
     if (rc) return rc;
     if (T) OZ2_HIP(hipEventRecord(T->ev[1], stream));
     // Column panels (testing knob GEMMUL8_CRT_PANELS; SURVEY 8 f3 "by cache residency", measured in profiles/r06_panel_crt*.txt): residue GEMMs of panel p,
@@ -590,6 +629,7 @@ int gemmul8_gemm(void* stream_, int dtype, int backend, int op_A, int op_B, size
         rc = gemmul8_crt(stream, dtype, backend, N, m, n, L.C_mid, L.mp, L.sizeC, L.sftA, L.sftB, alpha, beta, C, ldc);
         if (rc) return rc;
     }
+    if (nf) OZ2_HIP(launch_nonfinite_patch(stream, dtype, norm_op(op_A), norm_op(op_B), m, n, k, alpha, scalars_on_device(alpha), A, lda, B, ldb, L.sftA, L.sftB, C, ldc));
     if (T) {
         OZ2_HIP(hipEventRecord(T->ev[3], stream));
         OZ2_HIP(hipEventSynchronize(T->ev[3]));
@@ -644,6 +684,8 @@ int gemmul8_gemm_batched(void* stream_, int dtype, int backend, int op_A, int op
         ~Guard() { g_batch = BatchCtx{}; }
     } guard;
     char* w0 = align256(work);
+    const bool nf = g_nonfinite_mode.load(std::memory_order_relaxed) == 1;
+    const bool alpha_dev = nf && scalars_on_device(alpha);
     for (size_t b0 = 0; b0 < batch; b0 += 65535) {  // gridDim.z limit
         const size_t nb = std::min<size_t>(65535, batch - b0);
         const char* Ab = (const char*)A + (long long)b0 * strideA * (long long)esz;
@@ -658,12 +700,14 @@ int gemmul8_gemm_batched(void* stream_, int dtype, int backend, int op_A, int op
         g_batch.sa = (size_t)(strideA * (long long)esz);  // negative strides wrap: pointer arithmetic is modular
         g_batch.sb = (size_t)(strideB * (long long)esz);
         g_batch.sc = (size_t)(strideC * (long long)esz);
-        rc = gemmul8_scale(stream_, dtype, backend, op_A, op_B, m, n, k, Ab, lda, Bb, ldb, N, fastmode, 0, N, &L, 0, 0);
+        rc = scale_nf(stream_, dtype, backend, op_A, op_B, m, n, k, Ab, lda, Bb, ldb, N, fastmode, 0, N, &L, 0, 0, nf);
         if (rc) return rc;
         rc = gemmul8_lowprec_gemm(stream_, dtype, backend, m, n, k, N, 0, N, &L);
         if (rc) return rc;
         rc = gemmul8_crt(stream_, dtype, backend, N, m, n, L.C_mid, L.mp, L.sizeC, L.sftA, L.sftB, alpha, beta, Cb, ldc);
         if (rc) return rc;
+        if (nf)
+            OZ2_HIP(launch_nonfinite_patch((hipStream_t)stream_, dtype, norm_op(op_A), norm_op(op_B), m, n, k, alpha, alpha_dev, Ab, lda, Bb, ldb, L.sftA, L.sftB, Cb, ldc));
     }
     return GEMMUL8_OK;
 }

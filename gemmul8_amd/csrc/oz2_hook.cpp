@@ -63,6 +63,7 @@ struct Abi {
     decltype(&::gemmul8_dist_allgather_c) dist_allgather_c = nullptr;
     decltype(&::gemmul8_dist_destroy) dist_destroy = nullptr;
     decltype(&::gemmul8_set_fp8_bound_mode) set_fp8_bound_mode = nullptr;
+    decltype(&::gemmul8_set_nonfinite_mode) set_nonfinite_mode = nullptr;
 };
 const Abi& abi() {
     static const Abi a = [] {
@@ -102,7 +103,8 @@ const Abi& abi() {
         r.dist_allgather_c = (decltype(r.dist_allgather_c))dlsym(h, "gemmul8_dist_allgather_c");
         r.dist_destroy = (decltype(r.dist_destroy))dlsym(h, "gemmul8_dist_destroy");
         r.set_fp8_bound_mode = (decltype(r.set_fp8_bound_mode))dlsym(h, "gemmul8_set_fp8_bound_mode");
-        if (!r.work_size || !r.gemm || !r.work_size_batched || !r.gemm_batched || !r.add_row_bias || !r.comm_from_env || !r.dist_create || !r.dist_gemm || !r.dist_allgather_c || !r.dist_destroy || !r.set_fp8_bound_mode) {
+        r.set_nonfinite_mode = (decltype(r.set_nonfinite_mode))dlsym(h, "gemmul8_set_nonfinite_mode");
+        if (!r.work_size || !r.gemm || !r.work_size_batched || !r.gemm_batched || !r.add_row_bias || !r.comm_from_env || !r.dist_create || !r.dist_gemm || !r.dist_allgather_c || !r.dist_destroy || !r.set_fp8_bound_mode || !r.set_nonfinite_mode) {
             std::fprintf(stderr, "[GEMMUL8 HOOK] libgemmul8.so lacks the C ABI entry points\n");
             std::abort();
         }
@@ -122,6 +124,15 @@ const Abi& abi() {
 #define gemmul8_dist_allgather_c abi().dist_allgather_c
 #define gemmul8_dist_destroy abi().dist_destroy
 #define gemmul8_set_fp8_bound_mode abi().set_fp8_bound_mode
+namespace {
+int (*nonfinite_setter())(int) { return abi().set_nonfinite_mode; }
+}  // namespace
+#else
+// weak: a build that links this file against a library without the setter (tests/sanitize/mock_gpu.cpp) still loads; the mode then stays 0
+extern "C" __attribute__((weak)) int gemmul8_set_nonfinite_mode(int mode);
+namespace {
+int (*nonfinite_setter())(int) { return &gemmul8_set_nonfinite_mode; }
+}  // namespace
 #endif
 
 namespace {
@@ -215,6 +226,15 @@ void init_max_workspace() {
         // engine-safe default (include/gemmul8_c.h, gemmul8_set_fp8_bound_mode)
         if (const char* fb = std::getenv("GEMMUL8_FP8_BOUND"))
             if (!std::strcmp(fb, "reference")) (void)gemmul8_set_fp8_bound_mode(1);
+        // GEMMUL8_NONFINITE=ieee: BLAS-like NaN / Inf propagation (include/gemmul8_c.h, gemmul8_set_nonfinite_mode); unset or `reference`: mode 0.
+        // Not applied to the calls the multi-GPU plans take (GEMMUL8_DIST).
+        if (const char* nf = std::getenv("GEMMUL8_NONFINITE"); nf && *nf) {
+            if (!std::strcmp(nf, "ieee")) {
+                if (int (*set)(int) = nonfinite_setter()) (void)set(1);
+            } else if (std::strcmp(nf, "reference")) {
+                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=%s not understood (ieee | reference): non-finite mode 0\n", nf);
+            }
+        }
         const size_t mm = env_u64("GEMMUL8_MAX_M", 0), mn = env_u64("GEMMUL8_MAX_N", 0), mk = env_u64("GEMMUL8_MAX_K", 0);
         const unsigned mmod = (unsigned)env_u64("GEMMUL8_MAX_NUM_MOD", 2);
         const bool cplx = env_u64("GEMMUL8_NUM_MOD_Z", 0) > 0 || env_u64("GEMMUL8_NUM_MOD_C", 0) > 0;

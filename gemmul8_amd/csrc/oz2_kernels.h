@@ -87,7 +87,7 @@ hipError_t launch_amax_pair(hipStream_t stream, int dtype, size_t k, const Extra
 hipError_t launch_extract_pair(hipStream_t stream, int dtype, int backend, size_t k, size_t kp, const ExtractOperand& A, const ExtractOperand& B, void* zero_p,
                                size_t zero_bytes);
 hipError_t launch_shift_finalize(hipStream_t stream, int backend, unsigned N, size_t rowsA, const int* maxA, int16_t* sftA, size_t rowsB,
-                                 const int* maxB, int16_t* sftB);
+                                 const int* maxB, int16_t* sftB, bool nf = false);
 // one operand of the quantise / fast-shift launches; rows == 0 = absent (skip-scaling: the cached planes and shifts are kept)
 struct QuantOperand {
     bool kmajor = false, conj = false;
@@ -104,6 +104,7 @@ struct QuantOperand {
     const int16_t* fin_sft0 = nullptr;
     const int* fin_max = nullptr;
     float fin_log2P = 0.0f;
+    bool nf = false;  // non-finite mode 1 (oz2_nonfinite.hip): a row whose shift is kNonfiniteSft gets zero planes (the finalize keeps the sentinel)
 };
 // FP8 backend: the residue planes are FP6 panel images whenever B's last row block fits its share of the reference's plane size
 // (16-row granules at 3/4 byte per element: n >= 45; 64 keeps whole wave tiles); GEMMUL8_FP8_PLANES=e4m3 keeps the e4m3 byte planes
@@ -112,6 +113,29 @@ inline bool f6_planes_ok(size_t n) { return n >= 64 && knobs().fp8_planes != 1; 
 hipError_t launch_fast_shift_pair(hipStream_t stream, int dtype, int backend, unsigned N, size_t k, const QuantOperand& A, const QuantOperand& B);
 hipError_t launch_quantise_pair(hipStream_t stream, int dtype, int backend, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A,
                                 const QuantOperand& B);
+
+// ---- non-finite mode 1 (gemmul8_set_nonfinite_mode; oz2_nonfinite.hip)
+// the shift of a flagged row of op(A) / column of op(B) (one holding a NaN or an Inf): no mode-0 shift comes near it (a few thousand at most),
+// and the CRT's scalbn(R, sftA[i] + sftB[j]) of the finite R is +-0 with it
+constexpr int16_t kNonfiniteSft = INT16_MIN;
+constexpr int kNonfiniteShift = -(int)kNonfiniteSft;  // the same as a (positive) row shift of the quantisers
+// one operand of the flag launch; rows == 0 = absent (skip-scaling: the cached shifts keep their flags)
+struct FlagOperand {
+    bool kmajor = false;
+    size_t rows = 0;
+    const void* X = nullptr;
+    size_t ld = 0;
+    size_t xstride = 0;         // batched launch: bytes between the items' operands
+    int16_t* sft = nullptr;     // the shifts (fast mode: final; accurate mode: preliminary) ...
+    int16_t* sft_keep = nullptr;  // ... and, accurate mode, their scratch copy
+    int8_t* bound = nullptr;    // accurate mode: bound plane(s), zeroed for a flagged row before the bound GEMM
+    size_t kp = 0, parts = 0, part_stride = 0;
+};
+// flags both operands in ONE launch: reads every element once; run after the shifts are written and before anything consumes them
+hipError_t launch_flag_pair(hipStream_t stream, int dtype, size_t k, const FlagOperand& A, const FlagOperand& B);
+// after the CRT: C[i,j] = alpha * s + C[i,j] for every entry in a flagged row or column (s: the IEEE sum of op(A)[i,:] op(B)[:,j]); ops 0/1/2
+hipError_t launch_nonfinite_patch(hipStream_t stream, int dtype, int opA, int opB, size_t m, size_t n, size_t k, const void* alpha, bool alpha_on_device,
+                                  const void* A, size_t lda, const void* B, size_t ldb, const int16_t* sftA, const int16_t* sftB, void* C, size_t ldc);
 
 // ---- CRT accumulation + inverse scaling (oz2_crt.hip)
 hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, size_t m, size_t n, const void* Cmid, size_t ld_mid,

@@ -185,6 +185,7 @@ struct StageArgs {
     int f6;               // MODE_MOD, FP8 backend: 1 = the planes are FP6 panel images (oz2_gemm_f6.hip), 0 = e4m3 bytes, K-major rows
     unsigned f6_last;     // index of the plane's last 256-row block ...
     unsigned f6_rp_last;  // ... and its rows in the images (A: 256, B: its rows rounded up to 16)
+    int nf;               // MODE_MOD, non-finite mode 1 (oz2_nonfinite.hip): a row whose shift is the sentinel gets zero planes, the finalize keeps it
 };
 // item blockIdx.z of a batched launch: every workspace pointer moves by bw, the operand by bx (both 0 for a single GEMM).  The offsets
 // are applied at the few points of use: a modified COPY of the argument block lands in scratch memory (the quantise kernels ran 6x
@@ -193,6 +194,10 @@ struct StageArgs {
 #define OZ2_ZX ((size_t)blockIdx.z * a.bx)
 __device__ __forceinline__ int fused_final_shift(const StageArgs& a, size_t row, bool writer, size_t zw) {
     const int s0 = ((const int16_t*)((const char*)a.fin_sft0 + zw))[row];
+    if (a.nf && s0 == kNonfiniteSft) {  // flagged row (non-finite mode 1): the sentinel stays
+        if (writer) ((int16_t*)((char*)a.fin_out + zw))[row] = kNonfiniteSft;
+        return kNonfiniteShift;
+    }
     const int amax = ((const int*)((const char*)a.fin_max + zw))[row];  // INT8: int32 maximum; FP8: bit pattern of a non-negative float
     int f = 0;
     if (amax > 0) {
@@ -541,8 +546,14 @@ template <typename T> __device__ __forceinline__ void emit4_mod_float(const Stag
 }
 
 template <typename T, int MODE>
-__device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0, const T (&v)[4], int s) {
+__device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0, const T (&vin)[4], int s) {
     using E = ET<T>;
+    T v[4] = {vin[0], vin[1], vin[2], vin[3]};
+    if (MODE == MODE_MOD && a.nf && s == kNonfiniteShift) {  // flagged row (non-finite mode 1): zero planes, the sentinel never reaches ldexp
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = E::zero();
+        s = 0;
+    }
     int8_t* out = a.lo + OZ2_ZW + ((MODE == MODE_MOD && a.f6) ? f6_lane_offset(a, row, k0) : row * a.kp + k0);
     if constexpr (MODE == MODE_BOUND) {
         if (a.backend == kFP8) {
@@ -1067,7 +1078,12 @@ template <typename T> __device__ __forceinline__ void stage_f6_body(const StageA
         }
     }
     if (row >= a.rows) return;
-    const int s = OZ2_ROW_SHIFT(a, row, k0 == 0);   // (k0 == 0: K-step 0, fragment column 0 -- one lane per row over the grid)
+    int s = OZ2_ROW_SHIFT(a, row, k0 == 0);   // (k0 == 0: K-step 0, fragment column 0 -- one lane per row over the grid)
+    if (a.nf && s == kNonfiniteShift) {  // flagged row (non-finite mode 1): zero planes
+#pragma unroll
+        for (int e = 0; e < 32; ++e) v[e] = ET<T>::zero();
+        s = 0;
+    }
     // xs = trunc(x 2^s): exact; a float operand's xs is a float again (24 significant bits), kept in 32 registers and widened pair by pair
     using XS = typename std::conditional<sizeof(T) == 4, float, double>::type;
     XS xs[32];
@@ -1406,6 +1422,7 @@ static StageArgs quantise_args(int backend, int t_begin, int t_end, size_t k, si
     }
     a.backend = backend;
     a.conj = o.conj;
+    a.nf = o.nf ? 1 : 0;
     a.t_begin = t_begin;
     a.t_end = t_end;
     a.mt = make_mod_table(backend);
@@ -1439,7 +1456,7 @@ hipError_t launch_quantise_pair(hipStream_t stream, int dtype, int backend, int 
 // ------------------------------------------------------------------ accurate-mode shift from the bound maxima
 // rows of A (blocks 0 .. blocksA-1) and columns of B (the remaining blocks) in ONE launch; either count may be 0
 __global__ void shift_finalize_kernel(size_t rowsA, const int* maxA, int16_t* sftA, unsigned blocksA, size_t rowsB, const int* maxB,
-                                      int16_t* sftB, float log2P, int float_max, size_t bw) {
+                                      int16_t* sftB, float log2P, int float_max, size_t bw, int nf) {
     {  // batched launch: item blockIdx.z (all four arrays live in the item's workspace)
         const size_t o = blockIdx.z * bw;
         maxA = (const int*)((const char*)maxA + o), maxB = (const int*)((const char*)maxB + o);
@@ -1455,15 +1472,16 @@ __global__ void shift_finalize_kernel(size_t rowsA, const int* maxA, int16_t* sf
         f = __float2int_rd(__fmaf_rd(-0x1.000006p-1f, l, log2P));
     }
     int16_t* sft = isB ? sftB : sftA;
+    if (nf && sft[r] == kNonfiniteSft) return;  // flagged (non-finite mode 1): the sentinel stays
     sft[r] = (int16_t)(-((int)sft[r] + f));
 }
 hipError_t launch_shift_finalize(hipStream_t stream, int backend, unsigned N, size_t rowsA, const int* maxA, int16_t* sftA, size_t rowsB,
-                                 const int* maxB, int16_t* sftB) {
+                                 const int* maxB, int16_t* sftB, bool nf) {
     const unsigned bA = (unsigned)((rowsA + 255) / 256), bB = (unsigned)((rowsB + 255) / 256);
     if (bA + bB == 0) return hipSuccess;
     const float log2P = backend == kINT8 ? GEMMUL8_LOG2P_INT8[N - 2] : GEMMUL8_LOG2P_FP8[N - 2];
     hipLaunchKernelGGL(shift_finalize_kernel, dim3(bA + bB, 1, g_batch.batch), dim3(256), 0, stream, rowsA, maxA, sftA, bA, rowsB, maxB, sftB, log2P,
-                       backend == kFP8 ? 1 : 0, g_batch.ws);
+                       backend == kFP8 ? 1 : 0, g_batch.ws, nf ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -70,7 +70,7 @@ typedef struct gemmul8_layout {
     void *A_lo, *B_lo;         /* plane (part,q) at X_lo + (part*num_mat_total + q)*sizeX, num_mat_total = num_mat (+1 if skip enabled) ... see part_strideX */
     size_t part_strideA, part_strideB; /* bytes between Re/Im/Re+Im plane sets */
     void *A_bound, *B_bound;   /* accurate-mode 7-bit bound planes (alias plane 0 unless skip enabled) */
-    int16_t *sftA, *sftB;      /* negated shift exponents */
+    int16_t *sftA, *sftB;      /* negated shift exponents (non-finite mode 1: INT16_MIN for a flagged row / column) */
     void *C_mid;               /* N residue planes [n][mp] (complex: interleaved re,im) */
     void *scratch;             /* the reference's C_hi region (free for row/col maxima etc.) */
     size_t scratch_bytes;
@@ -172,6 +172,28 @@ GEMMUL8_API int gemmul8_add_f64(void *stream, double *dst, const double *src, si
  *   2            mode 0's ku with the reference's complex combination (the round-3 default; kept for tests/test_gpu_fp8_bound.py).
  * Process-wide; returns the previous mode (>= 0) or GEMMUL8_E_ARG.  The hook sets mode 1 when GEMMUL8_FP8_BOUND=reference. */
 GEMMUL8_API int gemmul8_set_fp8_bound_mode(int mode);
+
+/* Non-finite operands (NaN, +-Inf) in gemmul8_gemm and gemmul8_gemm_batched (and so gemmul8::gemm / gemmLt and the hook's direct paths).
+ *   0 (default)  every operand is assumed finite; nothing defines what C holds when one is not (the reference's behaviour; the cheapest path).
+ *   1 ("ieee")   BLAS-like propagation.  A row i of op(A) (m x k) is FLAGGED if one of its elements is NaN or +-Inf, a column j of op(B)
+ *                (k x n) likewise; a complex element counts when either component does.
+ *     1. clean entries (row i and column j unflagged) are bit-identical to the mode-0 result of the same call on A' and B': op(A) with every
+ *        flagged row set to zero, op(B) with every flagged column set to zero.  A non-finite C under beta != 0 propagates through
+ *        fma(beta, C, alpha AB) as in mode 0; beta == 0 does not read C.
+ *     2. a flagged entry is alpha * s + fl(beta * C[i,j]) (alpha * s when beta == 0), s = the IEEE sum over k of op(A)[i,k] op(B)[k,j] in the
+ *        element type (complex: the textbook componentwise products, conjugated per op, and the textbook product alpha * s).  Every such s is
+ *        NaN or +-Inf, and its class does not depend on the order of the sum: NaN if a term is NaN, an Inf meets a 0, or +Inf and -Inf both
+ *        occur; otherwise the sign of the infinite terms.  (Finite terms whose sum overflows are not covered.)
+ *     3. alpha == 0 (also a device-resident alpha: tested on the device): A and B do not enter, C = beta * C everywhere.
+ *     4. skip-scaling: the flags live in the shift arrays (gemmul8_layout.sftA / sftB hold INT16_MIN for a flagged row / column), so a
+ *        cached operand keeps them with its planes and a call that reuses the cache behaves as if it had seen the operand again.
+ *     5. no host synchronisation (stream-ordered, capture-safe) and no extra workspace: gemmul8_work_size and the layout do not change.
+ *                Cost: one extra read of A and B (the flag launch) and one launch after the CRT that reads op(A)'s flagged rows against all of
+ *                op(B) and op(B)'s flagged columns against all of op(A): (flagged rows x n + flagged columns x m) x k element pairs.
+ * The phase-level entry points (gemmul8_scale*, gemmul8_lowprec_gemm, gemmul8_crt*) and the multi-GPU plans (include/gemmul8_dist.h, the
+ * hook under GEMMUL8_DIST) ignore the mode and behave as mode 0.  Process-wide; returns the previous mode (>= 0) or GEMMUL8_E_ARG for anything
+ * but 0 and 1.  The hook sets mode 1 when GEMMUL8_NONFINITE=ieee. */
+GEMMUL8_API int gemmul8_set_nonfinite_mode(int mode);
 
 /* What the hook does with a GEMM of this shape under the CURRENT value of GEMMUL8_MIN_FLOPS (oz2_hook.cpp below_floor): 1 = emulated,
  * 0 = handed to the native routine, GEMMUL8_E_ARG on bad arguments.  GEMMUL8_MIN_FLOPS unset, empty or 0: every selected call is emulated
