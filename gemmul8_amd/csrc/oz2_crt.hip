@@ -32,21 +32,16 @@ namespace oz2 {
 #ifndef OZ2_CRT_BLOCK
 #define OZ2_CRT_BLOCK 256  // threads per block of crt_kernel: 128 / 256 / 512 / 1024 -> 455 / 377 / 414 / 380 us at config 2 (tools/crt_ab.py)
 #endif
-#ifndef OZ2_CRT_NT
-#define OZ2_CRT_NT 1      // non-temporal residue loads (plain loads: 393 us)
-#endif
+// (the residue loads are non-temporal: plain loads 393 us there)
 #ifndef OZ2_CRT_LB
 #define OZ2_CRT_LB 8      // bytes per residue-plane load and thread (tools/crt_ab.py measures 8 against 16)
-#endif
-#ifndef OZ2_CRT_LDS_STORE
-#define OZ2_CRT_LDS_STORE 1  // 1: the wave's results go through LDS so that every store instruction writes 1 KiB of contiguous memory
 #endif
 
 // A thread's NV results are NV * sizeof(U) = J * 16 contiguous bytes of C, a wave's 64 threads own 64 * J * 16 contiguous bytes (when
 // they sit in one column).  Stored directly, store instruction j of the J would scatter 16-byte pieces at a J * 16-byte lane stride
 // (every instruction touches all of the wave's cache lines, a quarter or an eighth of each).  crt_wave_store sends the pieces through
 // the wave's private LDS slice and reads them back transposed: instruction j then writes bytes [1024 j, 1024 (j + 1)) -- lane-linear,
-// whole lines.  Chunk (lane l, piece j) lives at slot l * J + (j ^ f(l)), f(l) = (l / (16 / J)) % J: the 8 lanes of a
+// whole lines (crt_kernel takes this path whenever a thread owns more than one 16-byte piece).  Chunk (lane l, piece j) lives at slot l * J + (j ^ f(l)), f(l) = (l / (16 / J)) % J: the 8 lanes of a
 // ds_write_b128 group hit 8 different 16-byte bank slots, and the read side is a permutation inside 256-byte blocks (conflict-free).
 template <int J> __device__ __forceinline__ unsigned crt_slot(unsigned l, unsigned j) {
     if constexpr (J >= 2 && J <= 16) return l * J + (j ^ ((l / (16 / J)) % J));
@@ -68,10 +63,6 @@ template <int J> __device__ __forceinline__ void crt_wave_store(char* lds_wave, 
         __builtin_nontemporal_store(x, (V4*)(gdst + (size_t)c * 16));  // streaming: C is written once and not re-read by this kernel
     }
 }
-
-#ifndef OZ2_CRT_UNITS
-#define OZ2_CRT_UNITS 1  // row groups per thread; > 1: the residue vectors of group u + 1 are requested before group u is accumulated
-#endif
 
 template <typename MID, int LB, int COMPS> struct CrtVec {
     static constexpr int NV = LB / (int)sizeof(MID);
@@ -107,17 +98,7 @@ __device__ __forceinline__ void crt_load(const CrtArgs& a, const CrtPos& p, size
     for (unsigned t = 0; t < (unsigned)NMAX; ++t)
         if (t < a.N) {
             const RawV* src_ = (const RawV*)(base + (size_t)t * a.plane_stride * COMPS);
-#if defined(OZ2_CRT_ABL) && (OZ2_CRT_ABL & 2)  // timing probe: no residue loads
-            RawV raw;
-            {
-                const unsigned long long fake = (unsigned long long)gid * 0x9E3779B97F4A7C15ull + t;
-                __builtin_memcpy(&raw, &fake, 8);
-                if (LB == 16) __builtin_memcpy((char*)&raw + 8, &fake, 8);
-            }
-            (void)src_;
-#else
-            const RawV raw = OZ2_CRT_NT ? __builtin_nontemporal_load(src_) : *src_;
-#endif
+            const RawV raw = __builtin_nontemporal_load(src_);
             __builtin_memcpy(&c[t], &raw, LB);
         }
 }
@@ -235,9 +216,6 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
         const size_t i0f = (first - colf * row_groups) * ROWS;
         char* wdst = (char*)((U*)((char*)a.C + blockIdx.z * a.bc) + (colf * a.ldc + i0f) * COMPS);
         const bool wave_fast = last < total && last / row_groups == colf && i0f + (size_t)64 * ROWS <= a.m && ((uintptr_t)wdst & 15u) == 0;
-#if defined(OZ2_CRT_ABL) && (OZ2_CRT_ABL & 1)  // timing probe: no stores (the condition is never true)
-        if (wave_fast && outv[0] != (U)123.456) return;
-#endif
         if (wave_fast) {
             crt_wave_store<J>(stage + (size_t)(threadIdx.x >> 6) * 64 * OUTB, outv, wdst, lane);
             return;
@@ -260,7 +238,8 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
 
 // UNITS row groups per thread (consecutive 256-thread slabs of one workgroup): the loads of unit u + 1 are issued before unit u is
 // accumulated, so every wave keeps residue vectors in flight while its FP64 pipe is busy (the kernel's FP64 work -- byte extraction,
-// conversion and two FMAs per residue -- is ~2/3 of its HBM time: without the overlap they add up instead of hiding each other)
+// conversion and two FMAs per residue -- is ~2/3 of its HBM time: without the overlap they add up instead of hiding each other).
+// launch_crt instantiates UNITS = 1 only; the parameter is part of the kernels' names.
 #ifndef OZ2_CRT_WAVES
 #define OZ2_CRT_WAVES 4  // waves per SIMD the register allocation aims at (experiment switch)
 #endif
@@ -270,7 +249,7 @@ __global__ void __launch_bounds__(OZ2_CRT_BLOCK) __attribute__((amdgpu_waves_per
     constexpr int ROWS = LB / (COMPS * (int)sizeof(MID));  // LB = 8: 8 / 4 / 4 / 2 rows; wider vectors cost registers
     constexpr int OUTB = ROWS * COMPS * (int)sizeof(U);     // bytes of C per thread
     static_assert(OUTB % 16 == 0, "a thread's results are whole 16-byte pieces");
-    constexpr bool LDS_STORE = OZ2_CRT_LDS_STORE && OUTB > 16;
+    constexpr bool LDS_STORE = OUTB > 16;
     __shared__ __attribute__((aligned(16))) char stage[LDS_STORE ? OZ2_CRT_BLOCK * OUTB : 16];
     using Vec = typename CrtVec<MID, LB, COMPS>::Vec;
 
@@ -304,10 +283,6 @@ __global__ void __launch_bounds__(OZ2_CRT_BLOCK) __attribute__((amdgpu_waves_per
 // (8 for float) and a store instruction writes 1 KiB of contiguous memory without any transposition.  Accumulation order, reduction and
 // axpby forms are those of crt_unit: the results are bit-identical (tests/test_gpu_parity.py runs both kernels).
 // Eligibility (launch_crt): int8 residues, (m * COMPS) % 1024 == 0, 16-byte aligned plane slices and C columns.
-#ifndef OZ2_CRT_DMA
-#define OZ2_CRT_DMA 1
-#endif
-
 #ifndef OZ2_CRT_DMA_WAVES
 #define OZ2_CRT_DMA_WAVES 2  // waves per workgroup sharing one unit (1 / 2 / 4: 289 / 266 / 262 us real x 14, 728 / 668 / 697 us complex x 20): each wave fetches half the planes and accumulates half the j (twice
                              // the waves per CU for the same LDS)
@@ -687,7 +662,7 @@ hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, si
         // LDS-DMA form: int8 residues, whole 1024-byte units per column, 16-byte aligned slices and C columns
         const size_t comps = cplx ? 2 : 1, usz = is_f32(dtype) ? 4 : 8;
         const int force = knobs().crt_kernel;  // 1 = dma, 2 = reg: testing switch (default: dma when eligible and large enough)
-        const bool eligible = OZ2_CRT_DMA && i8 && (m * comps) % 1024 == 0 && (ld_mid * comps) % 16 == 0 && (plane_stride * comps) % 16 == 0 &&
+        const bool eligible = i8 && (m * comps) % 1024 == 0 && (ld_mid * comps) % 16 == 0 && (plane_stride * comps) % 16 == 0 &&
                               ((uintptr_t)Cmid & 15u) == 0 && ((uintptr_t)C & 15u) == 0 && ((uintptr_t)sftA & 3u) == 0 /* dword loads of two int16 shifts */ && (ldc * comps * usz) % 16 == 0 && (g_batch.ws & 15u) == 0 &&
                               (g_batch.sc & 15u) == 0;
         const size_t units = m * comps / 1024 * n;
@@ -709,15 +684,11 @@ hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, si
     }
     const size_t rows_per_thread = OZ2_CRT_LB / ((cplx ? 2 : 1) * (i8 ? 1 : 2));
     const size_t threads = ((m + rows_per_thread - 1) / rows_per_thread) * n;
-    // small problems keep one unit per thread (more workgroups); large ones take the prefetching form
-    const bool multi = OZ2_CRT_UNITS > 1 && threads >= (size_t)OZ2_CRT_BLOCK * OZ2_CRT_UNITS * 2048;
-    const size_t per_block = (size_t)OZ2_CRT_BLOCK * (multi ? OZ2_CRT_UNITS : 1);
-    dim3 grid((unsigned)((threads + per_block - 1) / per_block), 1, g_batch.batch);
+    dim3 grid((unsigned)((threads + OZ2_CRT_BLOCK - 1) / OZ2_CRT_BLOCK), 1, g_batch.batch);  // one unit per thread
 #define OZ2_CRT(U, CP, MID)                                                                                                      \
     do {                                                                                                                         \
-        if (multi) hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, OZ2_CRT_UNITS, 20>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a); \
-        else if (N <= 14) hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 14>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);       \
-        else hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 20>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);                    \
+        if (N > 14) hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 20>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);             \
+        else hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 14>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);                    \
     } while (0)
     if (i8) {
         switch (dtype) {

@@ -24,19 +24,12 @@ struct TileMap {
 // 32 consecutive tiles = 8 x 4 tiles sharing 8 + 4 operand panels in its L2, and all 8 XCDs work on the SAME plane and
 // the same 8 A panels, so the L2 misses of one chunk (<= 8 + 32 panels of one plane) are served by the 256 MiB
 // Infinity Cache instead of HBM.  The tail (< 264 blocks) is split contiguously over the XCDs.
-#ifndef OZ2_MAP_CHUNKED
-#define OZ2_MAP_CHUNKED 1
-#endif
-#ifndef OZ2_MAP_COLBLOCK
-#define OZ2_MAP_COLBLOCK 1  // 0: always walk the full width of a plane
-#endif
 // Tile-columns per column block for operand panels of kbytes bytes per row (0 = full width).  Walking the full width, every group of
 // 8 tile-rows touches ALL B panels of the plane; they stay in the 256 MiB Infinity Cache between row groups as long as they are not
 // much more than half of it (n = 16384, k = 8192: 128 MiB -- blocking costs 3 % there, A is re-streamed once per block).  Beyond
 // that (16384^2 x 16384: 256 MiB of B per plane) every row group re-read B from HBM: blocks of ~128 MiB of B panels recover it
 // (6 planes 16384^2 x 16384: 19.19 -> 18.32 ms, 12288^2 x 16384: 10.47 -> 10.24; profiles/archive/r03_map_colblock_ab.txt).
 inline int map_colblock(size_t tiles_n, size_t kbytes) {
-    if (!OZ2_MAP_COLBLOCK) return 0;
     if (const int w = knobs().map_colblock; w >= 0)  // testing switch (oz2_knobs.hpp): tile-columns per block, 0 = full width
         return w > 0 && (size_t)w < tiles_n ? w : 0;
     const size_t panel = (size_t)BN * kbytes;
@@ -51,7 +44,7 @@ __device__ __forceinline__ TileMap map_tile(int bid, int nwg, int tiles_m, int t
     const int tiles_per_plane = tiles_m * tiles_n;
     {
         const int xcd = bid & 7, idx = bid >> 3;
-        const int fc = OZ2_MAP_CHUNKED ? ((nwg >> 3) >> 5) : 0;  // full chunks of 256
+        const int fc = (nwg >> 3) >> 5;  // full chunks of 256
         if (idx < fc * 32) {
             bid = (idx >> 5) * 256 + xcd * 32 + (idx & 31);
         } else {
@@ -117,7 +110,7 @@ __device__ __forceinline__ void udivmod_magic(unsigned x, unsigned d, unsigned M
 __device__ __forceinline__ TileMap map_tile(int bid, int nwg, const TileMapArgs a) {  // by value: the laboratory kernels read it from the kernel-argument address space
     {
         const int xcd = bid & 7, idx = bid >> 3;
-        const int fc = OZ2_MAP_CHUNKED ? ((nwg >> 3) >> 5) : 0;  // full chunks of 256
+        const int fc = (nwg >> 3) >> 5;  // full chunks of 256
         if (idx < fc * 32) {
             bid = (idx >> 5) * 256 + xcd * 32 + (idx & 31);
         } else {

@@ -38,19 +38,12 @@ constexpr int F6_BKE = 128;          // elements per K-step (one MFMA)
 constexpr int F6_ROWB = 96;          // bytes per row and K-step
 constexpr int F6_SLOT = BM * F6_ROWB;  // 24 KiB per panel slot
 typedef int v6i __attribute__((ext_vector_type(6)));
-#ifndef OZ2_F6_SGB
-#define OZ2_F6_SGB 1
-#endif
-#ifdef OZ2_F6_PINGPONG
-constexpr int F6_NSLOT = 5;
-#else
 constexpr int F6_NSLOT = 6;
-#endif
 
 // The product kernel (v2): every wave is SELF-PIPELINED -- fragment sets double-buffered in its 256 registers, the reads of the next half K-step
 // and its share of the LDS-DMA interleaved one by one with the MFMAs of the current half (sched_group_barrier) -- and ONE workgroup barrier per
 // K-step.  With 16-cycle MFMAs a ping-pong LOAD segment (16 ds_reads + 6 DMA issues, 600+ cycles) is far longer than the partner's MFMA
-// segment (256 cycles): the ping-pong form below ran the matrix pipes ~40 % busy (config 3: 3.47 POP/s).  Six 24 KiB panel slots = three full
+// segment (256 cycles): the ping-pong first form (round 5; five slots, LOAD / MFMA segments as in oz2_gemm_f8.hip) ran the matrix pipes ~40 % busy (config 3: 3.47 POP/s).  Six 24 KiB panel slots = three full
 // stages: panel A(g) in slot 2 (g % 3), B(g) behind it.  Per K-step g and wave (K-steps counted ACROSS tiles: the panel stream is continuous):
 //   half 0: MFMAs of rows 0-63 (fragments aL, bcur: in registers) | reads of A rows 64-127 of panel g -> aH | DMA pieces 3-5 of panel g + 2
 //   wait vmcnt(6) lgkmcnt(0); barrier B_g                            (panel g + 1 has landed for everyone; every read of panel g is complete)
@@ -361,193 +354,6 @@ __global__ void __launch_bounds__(F8_THREADS) gemm_f6_kernel(const F8Args args) 
 #undef F6_FETCH_ADVANCE_LOOP
 }
 
-#ifdef OZ2_F6_PINGPONG  // the first form (round 5, kept for A/B builds: tools/build_probes.sh SRC=oz2_gemm_f6 pp="-DOZ2_F6_PINGPONG"): ping-pong LOAD / MFMA segments as in oz2_gemm_f8.hip, five slots
-template <int EPI>
-__global__ void __launch_bounds__(F8_THREADS) gemm_f6_pingpong_kernel(const F8Args args) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int KT1 = args.kp / F6_BKE;  // K-steps per segment
-    const int KT = KT1 * args.nseg;    // K-steps per tile
-    const int total = args.total_tiles;
-    const int G = gridDim.x;
-    const size_t blockbytes = (size_t)BM * (size_t)(args.kp / 4 * 3);  // one 256-row block of a plane
-
-    // LDS-DMA: a panel is 24 linear instructions of 1 KiB; the four waves fetching an operand issue six each (a shorter last block of B:
-    // lanes beyond the image re-read its last chunk).  Waves 0-3 fetch B (needed one K-step after issue), waves 4-7 A (two K-steps ahead).
-    const bool isB = wave < 4;
-    unsigned doff[6];
-    const int8_t* gsrc;
-    int gstep = 0;         // bytes between consecutive K-steps of the block: Rp * 96
-    long long gdelta = 0;  // nseg == 2: from the panel of K-step KT1 + j of segment 1's plane to K-step j of segment 2's plane
-    auto uniform = [](const int8_t* ptr) {
-        const unsigned long long v = (unsigned long long)ptr;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return (const int8_t*)(((unsigned long long)hi << 32) | lo);
-    };
-    auto rows_pad = [&](int tn) {  // rows of B's block tn in its panel images
-        const int nr = args.n - tn * BN;
-        return nr >= BN ? BN : ((nr + 15) & ~15);
-    };
-#define F6_SET_TILE(vb_)                                                                                                     \
-    do {                                                                                                                     \
-        const TileMap tmap_ = map_tile((vb_), total, args.map);                                                              \
-        const F8Plane pl_ = f8_plane(args, tmap_.plane);                                                                     \
-        const int rp_ = isB ? rows_pad(tmap_.tn) : BM;                                                                       \
-        gstep = rp_ * F6_ROWB;                                                                                               \
-        gsrc = uniform(isB ? args.B + pl_.boff + (size_t)args.planeB[pl_.tt] * args.strideB + (size_t)tmap_.tn * blockbytes   \
-                           : args.A + pl_.boff + (size_t)args.planeA[pl_.tt] * args.strideA + (size_t)tmap_.tm * blockbytes); \
-        gdelta = isB ? ((long long)args.planeB2[pl_.tt] - args.planeB[pl_.tt]) * (long long)args.strideB - (long long)KT1 * gstep \
-                     : ((long long)args.planeA2[pl_.tt] - args.planeA[pl_.tt]) * (long long)args.strideA - (long long)KT1 * gstep; \
-        const int last_ = rp_ * 6 - 1;                                                                                       \
-        _Pragma("unroll") for (int q = 0; q < 6; ++q) {                                                                      \
-            const int c_ = ((wave & 3) * 6 + q) * 64 + lane;                                                                 \
-            doff[q] = (unsigned)(c_ < last_ ? c_ : last_) * 16u;                                                             \
-        }                                                                                                                    \
-    } while (0)
-#define F6_DMA(src_, q_, stage_)                                                                                             \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((src_) + doff[q_]),                     \
-                                     (__attribute__((address_space(3))) void*)((stage_) + ((wave & 3) * 6 + (q_)) * 1024), 16, 0, 0)
-
-    const int wm = wave >> 2, wn = wave & 3;
-    const int r16 = lane & 15;
-    const int q = lane >> 4;
-    // this lane's fragment pieces inside a panel image (see the header): A blocks always have 256 rows
-    const int ax = (q * BM + wm * 128 + r16) * 16;
-    const int ay = 64 * BM + ((q >> 1) * 2 * BM + 2 * (wm * 128 + r16) + (q & 1)) * 8;
-
-    auto frag = [&](const char* px, const char* py) {  // 24 bytes: the six operand registers
-        const v4i lo = *(const v4i*)px;
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        const v2i hi = *(const v2i*)py;
-        return v8i{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], 0, 0};
-    };
-    constexpr int SC3 = (int)0x82828282u;  // E8M0 scale 2^3 for every block: (v / 8 * 8) (w / 8 * 8)
-
-    auto run = [&]<bool ISB>() {
-        int vb_next = blockIdx.x, kt_next = 0;
-        bool more = true;
-        int hs = ISB ? 1 : 0;  // slot of the panel to fetch
-        const int8_t* fsrc;
-        char* fdst;
-        F6_SET_TILE(vb_next);
-#define F6_FETCH_ADVANCE()                                                                                                   \
-    do {                                                                                                                     \
-        hs = hs + 2 >= F6_NSLOT ? hs + 2 - F6_NSLOT : hs + 2;                                                                \
-        if (more && ++kt_next == KT) {                                                                                       \
-            kt_next = 0;                                                                                                     \
-            vb_next += G;                                                                                                    \
-            more = vb_next < total;                                                                                          \
-            if (more) F6_SET_TILE(vb_next);                                                                                  \
-            else kt_next = KT - 1;                                                                                           \
-        }                                                                                                                    \
-    } while (0)
-#define F6_FETCH_BEGIN()                                                                                                     \
-    do {                                                                                                                     \
-        fsrc = gsrc + (long long)OZ2_HOOK_KSTEP(kt_next) * gstep + (kt_next >= KT1 ? gdelta : 0);                            \
-        fdst = smem + hs * F6_SLOT;                                                                                          \
-    } while (0)
-        F6_FETCH_BEGIN();
-#pragma unroll
-        for (int i = 0; i < 6; ++i) F6_DMA(fsrc, i, fdst);
-        if constexpr (!ISB) {
-            F6_FETCH_ADVANCE();
-            F6_FETCH_BEGIN();
-#pragma unroll
-            for (int i = 0; i < 6; ++i) F6_DMA(fsrc, i, fdst);
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        if (wm == 1) __builtin_amdgcn_s_barrier();
-        // Hazards as in oz2_gemm_f8.hip: a slot was last read two (A) / one (B) K-steps before its refill is issued; every wave finishes a
-        // K-step's LOAD segments (lgkmcnt(0) + barrier) before the leading half enters the next one; each wave drains the DMA the NEXT
-        // K-step needs in its last LOAD segment (A waves: everything but the 6 instructions just issued).
-        int sA = 0;  // slot of A(g); B(g) sits in the next slot
-        for (int vb = blockIdx.x; vb < total; vb += G) {
-            const TileMap tmap = map_tile(vb, total, args.map);
-            const int rpB = rows_pad(tmap.tn);
-            const int bx = (q * rpB + wn * 64 + r16) * 16;
-            const int by = 64 * rpB + ((q >> 1) * 2 * rpB + 2 * (wn * 64 + r16) + (q & 1)) * 8;
-            v4f acc[8][4];
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
-
-            for (int kt = 0; kt < KT; ++kt) {
-                const char* curA = smem + sA * F6_SLOT;
-                const char* curB = smem + (sA == F6_NSLOT - 1 ? 0 : sA + 1) * F6_SLOT;
-                sA = sA + 2 >= F6_NSLOT ? sA + 2 - F6_NSLOT : sA + 2;
-                F6_FETCH_ADVANCE();
-                F6_FETCH_BEGIN();
-                v8i bf[4];
-#pragma unroll
-                for (int ah = 0; ah < 2; ++ah) {  // LOAD segment ah of this K-step
-                    v8i af[4];
-                    if (OZ2_HOOK_DMA_ON(vb == (int)blockIdx.x)) {  // (laboratory hook: always true in the product)
-                        if constexpr (ISB) {
-                            if (ah == 0) {
-#pragma unroll
-                                for (int i = 0; i < 6; ++i) F6_DMA(fsrc, i, fdst);
-                            }
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) F6_DMA(fsrc, ah * 3 + i, fdst);
-                        }
-                    }
-                    if (ah == 0) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) bf[j] = frag(curB + bx + j * 256, curB + by + j * 256);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) af[i] = frag(curA + ax + (ah * 4 + i) * 256, curA + ay + (ah * 4 + i) * 256);
-                    if (ah == 1) {
-                        if (!ISB) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-                        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (ah == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            const int j = (i & 1) ? 3 - jj : jj;  // serpentine, as in the INT8 / e4m3 kernels
-                            acc[ah * 4 + i][j] =
-                                __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af[i], bf[j], acc[ah * 4 + i][j], 2, 2, 0, SC3, 0, SC3);
-                        }
-                    __builtin_amdgcn_s_setprio(0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (ah == 1 && ISB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            const int i0 = tmap.tm * BM + wm * 128, j0 = tmap.tn * BN + wn * 64;
-            const F8Plane pl = f8_plane(args, tmap.plane);
-            f8_epilogue_mod<EPI>(acc, args, pl, i0, j0, lane);
-        }
-    };
-    if (isB) run.template operator()<true>();
-    else run.template operator()<false>();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may outlive the workgroup
-    if (wm == 0) __builtin_amdgcn_s_barrier();
-#undef F6_SET_TILE
-#undef F6_DMA
-#undef F6_FETCH_BEGIN
-#undef F6_FETCH_ADVANCE
-}
-
-#endif
-
 static int num_cus() {
     static int n = 0;
     if (!n) {
@@ -564,9 +370,6 @@ template <int EPI> static hipError_t launch(hipStream_t stream, F8Args& a, int p
     int dev_ = 0;
     if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) dev_ = 0;
     if (!attr_set_dev[dev_].load(std::memory_order_acquire)) {
-#ifdef OZ2_F6_PINGPONG
-#define gemm_f6_kernel gemm_f6_pingpong_kernel
-#endif
         hipError_t e = hipFuncSetAttribute((const void*)gemm_f6_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, F6_NSLOT * F6_SLOT);
         if (e != hipSuccess) return e;
         attr_set_dev[dev_].store(true, std::memory_order_release);

@@ -58,14 +58,6 @@ namespace oz2 {
 #ifndef OZ2_KBAR_MAX_KP
 #define OZ2_KBAR_MAX_KP 5120  // padded k up to which the K-step-barrier schedule is used (see launch<EPI>); 0 = never, 1 << 30 = always.  Round 4 (after the epilogue / tile-prologue work): +1.0 / +1.3 % at k = 4608 / 5120 on 8192^2 x 14 planes, +0.5 % at 5120 on 16384^2 x 6; at 6144 +0.9 % / -1.1 %, at 7168 0 / -1.3 %, at 8192 -1.3 % (profiles/archive/r04_gemm_ab_kbar_threshold.txt)
 #endif
-#ifndef OZ2_KBAR_PEEL_FIRST
-#define OZ2_KBAR_PEEL_FIRST 0
-#endif
-#ifndef OZ2_MOD256
-#define OZ2_MOD256 0  // 1: K <= 256 launches carry their accumulators as float patterns (EPI_MOD256 / RED_MAGIC: two instead of three instructions per accumulator in the
-                      // residue epilogue).  Built and bit-identical in round 6, measured NEUTRAL (8192^2 x 128 / 256: -1 / -2 %, 16384^2 x 256: +1 %,
-                      // profiles/r06_short_k_epilogue_ab.txt): the instruction count is not what bounds that epilogue.  Not instantiated in the shipped library.
-#endif
 #ifndef OZ2_SLEEP_A
 #define OZ2_SLEEP_A 4  // s_sleep units (64 clocks) between the A producers' 8 groups of 2 LDS-DMA instructions
 #endif
@@ -96,10 +88,7 @@ struct NoCrt {
 // epilogue has reduced the four accumulator tiles of a sub-block (hook phase 0), four MFMAs on all-zero fragments with C = the start value rewrite them --
 // 32 matrix instructions per wave and tile on a pipe that has nothing else to do, instead of 128 v_mov_b32 at the head of the next tile on the vector
 // ALU that the two waves' epilogues (~650 instructions each) are bound by.
-#ifndef OZ2_KBAR_MFMA_REINIT
-#define OZ2_KBAR_MFMA_REINIT 1
-#endif
-template <bool ZERO> struct MfmaReinitHook {  // ZERO: the start value is 0 (short-K launches): the C operand is the inline constant
+template <bool ZERO> struct MfmaReinitHook {  // ZERO: the start value is 0 (short-K launches, the only instantiation): the C operand is the inline constant
     v4i (*acc)[4];
     int acc0;
     __device__ __forceinline__ void operator()(int sb, int phase) const {
@@ -120,7 +109,6 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
     static_assert(FUSE == 0, "the in-kernel CRT forms are laboratory code: tools/experiments/fused_crt");
 #endif
     static_assert(FUSE == 0 || EPI == EPI_MOD, "the CRT tail follows the real requantise epilogue");
-    static_assert(EPI != EPI_MOD256 || (KBAR && SMALLK && FUSE == 0), "the K <= 256 form is an instantiation of the short-K K-step-barrier kernel");
     static_assert(offsetof(CrtArgs, Cmid) == 0 && alignof(CrtArgs) == 8, "i8_crt_tail locates the block in the kernel-argument segment");
     (void)crt;
     const int planes_per_tile = FUSE ? args.planes : 1;
@@ -238,7 +226,7 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
         int sA = 0;  // slot of A(g); B(g) sits in the next slot (mod 5)
         // MFMA_REINIT: the accumulators live across the tile loop; the v_mov initialisation runs once, every later tile finds them rewritten by
         // the matrix pipe behind the previous epilogue (MfmaReinitHook)
-        constexpr bool MFMA_REINIT = OZ2_KBAR_MFMA_REINIT && SMALLK && (EPI == EPI_MOD || EPI == EPI_MOD256) && FUSE == 0;  // SMALLK only: with a register C operand (start value -2^31) the form measured -0.6 ... -1.6 % at k = 1024 / 2048 (profiles/r06_short_k_epilogue_ab.txt)
+        constexpr bool MFMA_REINIT = SMALLK && EPI == EPI_MOD && FUSE == 0;  // SMALLK only: with a register C operand (start value -2^31) the form measured -0.6 ... -1.6 % at k = 1024 / 2048 (profiles/r06_short_k_epilogue_ab.txt)
         v4i acc[8][4];
         if constexpr (MFMA_REINIT) {
 #pragma unroll
@@ -252,11 +240,9 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
             const PlaneConsts pcon = (FUSE || EPI == EPI_MAX) ? PlaneConsts{} : plane_consts(args, pref);  // fetched here: the latency passes behind the K loop
             for (int pl = 0; pl < planes_per_tile; ++pl) {
             v4i af[4], bf[4];
-            // PEEL_FIRST (round 6, NOT enabled: -DOZ2_KBAR_PEEL_FIRST=1): SMALLK (k <= 512: accumulators start at 0) without the 128 v_mov_b32 per wave and
-            // tile -- the first K-step's MFMAs take the inline constant 0 as their C operand.  The compiler then moves seven accumulator quads through
-            // scratch INSIDE the peeled K-step (140 bytes; the peeled copy's results and the loop's registers do not coalesce), as with round 4's attempt.
-            constexpr bool PEEL_FIRST = OZ2_KBAR_PEEL_FIRST && SMALLK && EPI == EPI_MOD && FUSE == 0;
-            if constexpr (!PEEL_FIRST && !MFMA_REINIT) {
+            // (Peeling the first K-step of short-K launches, its MFMAs taking the inline constant 0 as their C operand instead of the 128 v_mov_b32 per wave and
+            // tile, was tried in rounds 4 and 6: the compiler then moves seven accumulator quads through scratch INSIDE the peeled K-step, 140 bytes.  Withdrawn.)
+            if constexpr (!MFMA_REINIT) {
 #pragma unroll
             for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -277,17 +263,14 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
         }                                                                                                                    \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) { af[i] = *(const v4i*)(curA + (((seg_) & 1) * 4 + i) * 16 * BK + coff_); OZ2_KBAR_PIN(); } \
     } while (0)
-#define OZ2_MMA_SEG(seg_, first_)                                                                                            \
+#define OZ2_MMA_SEG(seg_)                                                                                            \
     do {                                                                                                                     \
         OZ2_KBAR_WAIT();                                                                   \
         __builtin_amdgcn_sched_barrier(0);                                                                                   \
         __builtin_amdgcn_s_setprio(1);                                                                                       \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) {                     \
             const int j = (i & 1) ? 3 - jj : jj; /* serpentine: see the ping-pong branch */                                   \
-            if ((first_) && (seg_) < 2) /* the K-step's first touch of these accumulators: C = 0 */                          \
-                acc[((seg_) & 1) * 4 + i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[j], v4i{0, 0, 0, 0}, 0, 0, 0); \
-            else                                                                                                             \
-                acc[((seg_) & 1) * 4 + i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[j], acc[((seg_) & 1) * 4 + i][j], 0, 0, 0); \
+            acc[((seg_) & 1) * 4 + i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[j], acc[((seg_) & 1) * 4 + i][j], 0, 0, 0); \
         }                                                                                                                    \
         __builtin_amdgcn_s_setprio(0);                                                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                                   \
@@ -302,7 +285,7 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
             const int nph = (EPI == EPI_MAX && args.kt_mid > 0) ? 2 : 1;
             for (int ph = 0; ph < nph; ++ph) {
             const int kt_end = (EPI == EPI_MAX && ph + 1 < nph) ? args.kt_mid : KT;
-            auto kstep = [&]<bool FIRST>() {
+            auto kstep = [&]() {
                 OZ2_SET_PANELS();
 #pragma unroll
                 for (int seg = 0; seg < 4; ++seg) {
@@ -315,18 +298,14 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
                         __builtin_amdgcn_s_barrier();
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    OZ2_MMA_SEG(seg, FIRST);
+                    OZ2_MMA_SEG(seg);
                 }
                 if (!WM1) {
                     __builtin_amdgcn_s_barrier();
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            if constexpr (PEEL_FIRST) {  // (one phase, kt == 0 here, KT >= 2)
-                kstep.template operator()<true>();
-                ++kt;
-            }
-            for (; kt < kt_end; ++kt) kstep.template operator()<false>();
+            for (; kt < kt_end; ++kt) kstep();
 #undef OZ2_SET_PANELS
 #undef OZ2_LOAD_SEG
 #undef OZ2_MMA_SEG
@@ -339,11 +318,8 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
 #pragma unroll
                 for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
 #else
-#ifndef OZ2_KBAR_EPI_LANE_LIVE
-#define OZ2_KBAR_EPI_LANE_LIVE 0
-#endif
             int lane_e = lane;
-            if constexpr (!OZ2_KBAR_EPI_LANE_LIVE && (EPI == EPI_MOD || EPI == EPI_MOD256)) {  // (the complex combine keeps the live lane id: recomputed there, 116 bytes of accumulator spills appear in its K loop)
+            if constexpr (EPI == EPI_MOD) {  // (the complex combine keeps the live lane id: recomputed there, 116 bytes of accumulator spills appear in its K loop)
             // The lane id of the epilogue is RECOMPUTED here (two v_mbcnt behind an opaque asm, so that it is not hoisted): kept live across the K loop it was
             // spilled (12 bytes of scratch), and the reload's vmcnt(0) made every tile wait for the PREVIOUS tile's residue stores to be acknowledged --
             // free behind a long K loop, a stall of the order of the store latency at k <= 1024 where the K loop is 2-8 us (round 6).  The consumer waves
@@ -354,7 +330,7 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
             }
             if constexpr (FUSE != 0) i8_epilogue<EPI, NoHook, -1>(acc, args, PlaneRef{0, pl}, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e);
             else if constexpr (EPI == EPI_MAX) i8_epilogue<EPI, NoHook, 0>(acc, args, plane_ref(args, tmap.plane), PlaneConsts{}, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e);
-            else if constexpr (MFMA_REINIT) i8_epilogue<EPI, MfmaReinitHook<EPI != EPI_MOD256>, (int)SMALLK>(acc, args, pref, pcon, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e, MfmaReinitHook<EPI != EPI_MOD256>{acc, args.acc0});
+            else if constexpr (MFMA_REINIT) i8_epilogue<EPI, MfmaReinitHook<true>, (int)SMALLK>(acc, args, pref, pcon, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e, MfmaReinitHook<true>{acc, args.acc0});
             else i8_epilogue<EPI, NoHook, (int)SMALLK>(acc, args, pref, pcon, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e);
 #endif
             }  // phase
@@ -458,13 +434,6 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
     }
 }
 
-#ifdef OZ2_LAB_SELFPIPE  // laboratory build only (tools/build_probes.sh sp="-DOZ2_LAB_SELFPIPE=1"): the self-pipelined 8-wave form of the residue GEMM
-#include "../../tools/experiments/gemm_i8_selfpipe.inc"
-#endif
-#ifdef OZ2_LAB_W4  // laboratory build only (tools/build_probes.sh w4="-DOZ2_LAB_W4=1"): four waves x 512 registers, wave tile 128 x 128
-#include "../../tools/experiments/gemm_i8_w4.inc"
-#endif
-
 static void fill_common(GemmArgs& a, size_t kp, size_t m, size_t n) {
     a.kp = (int)kp;
     a.m = (int)m;
@@ -533,52 +502,8 @@ template <int EPI> static hipError_t launch(hipStream_t stream, GemmArgs& a, int
     // (the bound GEMM keeps the ping-pong schedule at every k.  In round 2 its K-step-barrier instantiation spilled accumulators INSIDE
     // the MFMA loop; with the round-3 source it no longer does, but the single-plane launch still runs slower with it: bounds phase
     // 88.4 -> 92.4 us at 3072^3, 130.9 -> 134.6 at 4096^3, equal at 2048^3 and 8192^3.  round-3 A/B: profiles/archive/r03_bound_ab.txt)
-#ifdef OZ2_LAB_SHORTK  // laboratory build only (tools/experiments/shortk): the half-tile ping-pong kernel for padded k <= OZ2_LAB_SHORTK
-    if constexpr (EPI != EPI_MAX) {
-        if (a.nseg == 1 && a.kp <= OZ2_LAB_SHORTK) return launch_gemm_i8_shortk(stream, a, EPI);
-    }
-#endif
-#ifdef OZ2_LAB_SELFPIPE
-    if constexpr (EPI != EPI_MAX) {
-        if (a.nseg == 1) {
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void*)gemm_i8_selfpipe_kernel<EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES);
-                (void)hipFuncSetAttribute((const void*)gemm_i8_selfpipe_kernel<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES);
-                attr_set = true;
-            }
-            int grid = num_cus() & ~7;
-            if (a.total_tiles < grid) grid = a.total_tiles;
-            if (a.acc0 == 0) hipLaunchKernelGGL((gemm_i8_selfpipe_kernel<EPI, true>), dim3(grid), dim3(512), RING_LDS_BYTES, stream, a);
-            else hipLaunchKernelGGL((gemm_i8_selfpipe_kernel<EPI, false>), dim3(grid), dim3(512), RING_LDS_BYTES, stream, a);
-            return hipGetLastError();
-        }
-    }
-#endif
-#ifdef OZ2_LAB_W4
-    if constexpr (EPI != EPI_MAX) {
-        if (a.nseg == 1 && a.kp >= 4 * BK) {
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void*)gemm_i8_w4_kernel<EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES);
-                (void)hipFuncSetAttribute((const void*)gemm_i8_w4_kernel<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES);
-                attr_set = true;
-            }
-            int grid = num_cus() & ~7;
-            if (a.total_tiles < grid) grid = a.total_tiles;
-            if (a.acc0 == 0) hipLaunchKernelGGL((gemm_i8_w4_kernel<EPI, true>), dim3(grid), dim3(256), RING_LDS_BYTES, stream, a);
-            else hipLaunchKernelGGL((gemm_i8_w4_kernel<EPI, false>), dim3(grid), dim3(256), RING_LDS_BYTES, stream, a);
-            return hipGetLastError();
-        }
-    }
-#endif
-    if constexpr (EPI == EPI_MOD && OZ2_MOD256) {
-        // K <= 256: accumulators carried as float patterns (RED_MAGIC, oz2_gemm_i8_epi.hpp): 8192^2 x 256, 14 planes: see profiles/r06_short_k_epilogue_ab.txt
-        if ((size_t)a.kp * (size_t)a.nseg <= 256) {
-            a.acc0 = 0x4B400000;
-            return launch_sched<EPI_MOD256, true, 0, true>(stream, a);
-        }
-    }
+    // (A float-pattern accumulator form for K <= 256 -- two instead of three instructions per accumulator in the residue epilogue -- was built in round 6:
+    // bit-identical, measured neutral, -1 / -2 % at 8192^2 x 128 / 256 and +1 % at 16384^2 x 256, profiles/r06_short_k_epilogue_ab.txt: retired.)
     if constexpr (EPI != EPI_MAX) {
         if (a.acc0 == 0) return launch_sched<EPI, true, 0, true>(stream, a);  // K <= 512
         if (a.kp * a.nseg <= OZ2_KBAR_MAX_KP) return launch_sched<EPI, true>(stream, a);

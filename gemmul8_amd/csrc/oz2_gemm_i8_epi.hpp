@@ -1,6 +1,6 @@
 // INT8 GEMM kernels, shared pieces: the kernel-argument block and the fused epilogues on a wave's 128 x 64 accumulator block (requantise
 // EPI_MOD / complex combine EPI_CPLX / bound maxima EPI_MAX).  Used by the persistent 256 x 256-tile kernel (oz2_gemm_i8.hip) and by the
-// short-K kernel (oz2_gemm_i8_shortk.hip).  Replaces src/conv_hi2mid_real.hpp:9-25, src/conv_hi2mid_complex.hpp:9-127 and the maxima passes
+// laboratory build of its in-kernel CRT forms (tools/experiments/fused_crt).  Replaces src/conv_hi2mid_real.hpp:9-25, src/conv_hi2mid_complex.hpp:9-127 and the maxima passes
 // src/scaling_accu_real.hpp:142-226, src/scaling_accu_complex.hpp:132-224 of the reference: the INT32 accumulators never leave registers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,11 +11,11 @@
 
 namespace oz2 {
 
-// ---- Laboratory boundary.  The INT8 GEMM translation units (oz2_gemm_i8.hip, oz2_gemm_i8_shortk.hip) are the PRODUCT: they instantiate exactly the kernels gemmul8_gemm can reach and carry
+// ---- Laboratory boundary.  The INT8 GEMM translation unit (oz2_gemm_i8.hip) is the PRODUCT: it instantiates exactly the kernels gemmul8_gemm can reach and carries
 // no timing ablation.  Laboratory builds (tools/experiments/: real-data timing probes, the in-kernel CRT forms) compile a second TU that
 // defines OZ2_LAB_* and #includes this file; the shipped Makefile passes -DOZ2_PRODUCT_BUILD, which refuses every such macro, so no
 // -D in EXTRA can turn libgemmul8.so into a library that computes something else.
-#if defined(OZ2_PRODUCT_BUILD) && (defined(OZ2_LAB_HOOKS) || defined(OZ2_LAB_FUSED_CRT) || defined(OZ2_LAB_SHORTK) || defined(OZ2_LAB_SELFPIPE) || defined(OZ2_LAB_W4))
+#if defined(OZ2_PRODUCT_BUILD) && (defined(OZ2_LAB_HOOKS) || defined(OZ2_LAB_FUSED_CRT))
 #error "laboratory switches (OZ2_LAB_*) are not allowed in the product build of libgemmul8.so: use tools/experiments/"
 #endif
 #ifdef OZ2_LAB_HOOKS
@@ -34,7 +34,7 @@ namespace oz2 {
 #error "timing probes (OZ2_HOOK_SKIP_*) compute something else: not allowed in the product build of libgemmul8.so"
 #endif
 
-enum { EPI_MOD = 0, EPI_MAX = 1, EPI_CPLX = 2, EPI_MOD256 = 3 };  // EPI_MOD256 (round 6): EPI_MOD of launches with K <= 256, accumulators carried as float patterns (RED_MAGIC)
+enum { EPI_MOD = 0, EPI_MAX = 1, EPI_CPLX = 2 };
 
 struct GemmArgs {
     const int8_t* A[3];    // K-segment s of plane 0: A[s] + plane*strideA : [rows(pad 256)][kp]
@@ -101,7 +101,7 @@ enum { RED_ODD = 1, RED_ODD_SMALL = 3, RED_MAGIC = 4 };
 // three instructions -- measured 10 % SLOWER at k = 1024 (the dependent FP64 chains no longer overlap); separate run-time forms for p = 256 (low
 // byte) and for even p (32-bit multiply-high, no INT8 modulus needs it) existed until round 4 and cost far more than they saved (i8_epilogue).
 // Hook: called as hook(s, 0) before and hook(s, 1) after the stores of sub-block s = 2 tj + tg (64 rows x 16 columns; 8 per wave tile); NoHook
-// (nothing) in every product kernel -- the laboratory short-K kernel places its workgroup barriers there (tools/experiments/shortk).
+// (nothing) unless the kernel has work to place there (MfmaReinitHook, oz2_gemm_i8.hip).
 struct NoHook {
     __device__ __forceinline__ void operator()(int, int) const {}
 };
@@ -143,7 +143,6 @@ __device__ __forceinline__ void i8_epilogue_mod(const v4i (&acc)[8][4], const Ge
     const float invp = 1.0f / (float)p;
     [[maybe_unused]] const unsigned dotw = pc.dotw, dotc = pc.dotc;
     static_assert(RED == RED_ODD || RED == RED_ODD_SMALL || RED == RED_MAGIC, "one of the three reduction forms");
-    constexpr bool MODLIKE = EPI == EPI_MOD || EPI == EPI_MOD256;
     // RED_ODD_SMALL, short K (kp * nseg <= 512: |x| <= 512 * 127^2 < 2^23; the accumulators start at 0, GemmArgs.acc0): the quotient comes
     // straight from the accumulator -- v_cvt_f32_i32, one fma against 1.5 * 2^23 (its low 24 bits are 2^22 + q for either sign
     // of q), v_mad_i32_i24: the canonical residue minus p 2^22, i.e. the canonical LOW BYTE, which is all the epilogue stores.
@@ -174,11 +173,12 @@ __device__ __forceinline__ void i8_epilogue_mod(const v4i (&acc)[8][4], const Ge
         asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r0) : "v"(__float_as_int(qm[0])), "s"(-p), "v"(u0));
         asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r1) : "v"(__float_as_int(qm[1])), "s"(-p), "v"(u1));
     };
-    // RED_MAGIC, K <= 256 (round 6): the accumulators start at 0x4B400000 (GemmArgs.acc0), the bit pattern of the float 1.5 * 2^23; an int32 sum |x| <= 256 * 128^2 = 2^22
-    // added to it as an INTEGER leaves the pattern of the float 1.5 * 2^23 + x (ulp 1 on [2^23, 2^24], both ends representable).  So the conversion of RED_ODD_SMALL
-    // becomes a packed subtraction on two accumulators, its fma a packed fma with the very same operands (same quotient, bit for bit), and v_mad_i32_i24 finishes on
-    // the biased register: the bias has no bit below 2^22, the low byte -- all the epilogue keeps -- is that of x - q p.  Two instructions per accumulator instead of
-    // three (~20 % of the epilogue's vector-ALU work; CPU model: tests/test_residue_math.py::test_magic_bias_reduction).
+    // RED_MAGIC, K <= 256 (round 6; NOT instantiated: bit-identical and measured neutral, -1 / -2 % at 8192^2 x 128 / 256, +1 % at 16384^2 x 256,
+    // profiles/r06_short_k_epilogue_ab.txt -- its kernel instantiation, launch rule and -D switch are retired).  Accumulators that start at 0x4B400000, the bit pattern
+    // of the float 1.5 * 2^23, plus an int32 sum |x| <= 256 * 128^2 = 2^22 read as the float 1.5 * 2^23 + x: the conversion of RED_ODD_SMALL becomes a packed subtraction
+    // on two accumulators, its fma a packed fma with the same operands, and v_mad_i32_i24 finishes on the biased register (the bias has no bit below 2^22).  CPU model:
+    // tests/test_residue_math.py::test_magic_bias_reduction.  The form stays in the source because the closure below is part of every instantiation of this function:
+    // without it the compiler numbers the basic blocks of the complex kernels differently, and the switch retirement was held to byte-identical assembly listings.
     [[maybe_unused]] auto red_magic_pair = [&](int x0, int x1, int& r0, int& r1) {
         typedef float v2f __attribute__((ext_vector_type(2)));
         const v2f xm = {__int_as_float(x0), __int_as_float(x1)};
@@ -223,7 +223,7 @@ __device__ __forceinline__ void i8_epilogue_mod(const v4i (&acc)[8][4], const Ge
         const auto w23 = __builtin_amdgcn_permlane16_swap(s0[1], s1[1], false, false);  //         rows 8-11, rows 12-15
         z[0] = w01[0], z[1] = w01[1], z[2] = w23[0], z[3] = w23[1];
     };
-    if constexpr (MODLIKE) {
+    if constexpr (EPI == EPI_MOD) {
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj) {
             const int col = j0 + tj * 16 + c16;
@@ -316,15 +316,13 @@ __device__ __forceinline__ void i8_epilogue(const v4i (&acc)[8][4], const GemmAr
     const int c16 = lane & 15;
     const int q = lane >> 4;
 
-    if constexpr (EPI == EPI_MOD256) {
-        i8_epilogue_mod<EPI, RED_MAGIC, Hook>(acc, args, pl, pc, i0, j0, lane, hook);
-    } else if constexpr (EPI == EPI_MOD || EPI == EPI_CPLX) {
+    if constexpr (EPI == EPI_MOD || EPI == EPI_CPLX) {
         // ONE reduction form per kernel instantiation (SMALLK: the launch's accumulators start at 0, K <= 512).  p = 256 takes the odd-modulus forms too:
         // the only thing the epilogue keeps of a residue is its low byte, and for p = 256 every quotient leaves the low byte of the accumulator
         // in place (dotw = 1, dotc = 0).  Until round 4 the epilogue was a run-time chain of four forms (256 / small / odd / generic); the
         // structurizer lays such a chain out as a straight line of predicated blocks, which keeps the accumulators live through the whole
         // epilogue of every form but the last -- no accumulator register could be reused inside an epilogue.
-        // SMALLK < 0: the form is chosen at run time from GemmArgs.acc0 (laboratory kernels).
+        // SMALLK < 0: the form is chosen at run time from GemmArgs.acc0 (the laboratory's in-kernel CRT forms).
         if constexpr (SMALLK > 0) i8_epilogue_mod<EPI, RED_ODD_SMALL, Hook>(acc, args, pl, pc, i0, j0, lane, hook);
         else if constexpr (SMALLK == 0) i8_epilogue_mod<EPI, RED_ODD, Hook>(acc, args, pl, pc, i0, j0, lane, hook);
         else if (args.acc0 == 0) i8_epilogue_mod<EPI, RED_ODD_SMALL, Hook>(acc, args, pl, pc, i0, j0, lane, hook);
@@ -376,9 +374,5 @@ template <int EPI, typename Hook = NoHook, int SMALLK = -1>
 __device__ __forceinline__ void i8_epilogue(const v4i (&acc)[8][4], const GemmArgs& args, PlaneRef pl, int i0, int j0, int lane, Hook hook = {}) {
     i8_epilogue<EPI, Hook, SMALLK>(acc, args, pl, EPI == EPI_MAX ? PlaneConsts{} : plane_consts(args, pl), i0, j0, lane, hook);
 }
-
-#ifdef OZ2_LAB_SHORTK  // laboratory kernel (tools/experiments/shortk/oz2_gemm_i8_shortk.hip); `a` complete as launch<EPI> of oz2_gemm_i8.hip leaves it
-hipError_t launch_gemm_i8_shortk(hipStream_t stream, const GemmArgs& a, int epi);
-#endif
 
 }  // namespace oz2

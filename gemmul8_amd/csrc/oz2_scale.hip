@@ -99,52 +99,23 @@ template <typename U> __device__ __forceinline__ U wave_max(U v) {
 // ------------------------------------------------------------------ stage kernel (extract / quantise)
 enum { MODE_BOUND = 0, MODE_MOD = 1 };
 
-#ifndef OZ2_STAGE_V16
-#define OZ2_STAGE_V16 0  // 1: INT8 residue planes leave as 16-byte stores (4 x 4 dword transpose over the lane quads) instead of one dword per
-                         // lane and plane.  Measured SLOWER (quantise pair 8192^2 x 14 planes: 702 vs 672 us, profiles/archive/r03_hbm_ab.txt): the kernel is
-                         // bound by VALU issue, not by its store pattern, and the transposes add 16 operations per 4 planes -- kept for reference
-#endif
-#ifndef OZ2_STAGE_VLOAD
-#define OZ2_STAGE_VLOAD 1  // K-major operands: a thread's 4 consecutive elements as 16-byte non-temporal loads (672 -> 660 us); 0: element-wise loads
-#endif
+// INT8 residue planes leave as one dword per lane and plane.  16-byte stores (a 4 x 4 dword transpose over the lane quads) measured slower, quantise pair
+// 8192^2 x 14 planes 702 vs 672 us (profiles/archive/r03_hbm_ab.txt): the kernel is bound by VALU issue, not by its store pattern.
+// K-major operands: a thread's 4 consecutive elements come as 16-byte non-temporal loads (672 -> 660 us against element-wise loads).
 
-// 4 x 4 transpose of dwords over a lane quad (lanes 4i .. 4i+3): on return w[j] holds what lane j of the quad had in w[q], q = own lane
-// & 3.  Two butterfly stages of quad_perm DPP moves (full rate, no LDS): 16 VALU operations.  The four lanes of a quad own 16
-// consecutive k of one row and each produced one dword (4 residues) per plane: after the transpose lane q owns the 16 residues of plane
-// t0 + q -- ONE 16-byte store per lane instead of four dword stores.
-__device__ __forceinline__ void quad_transpose4(unsigned (&w)[4], unsigned q) {
-    const bool o1 = q & 1u, o2 = q & 2u;
-#pragma unroll
-    for (int p = 0; p < 4; p += 2) {  // exchange with lane ^ 1: pairs (w0, w1), (w2, w3)
-        const unsigned snd = o1 ? w[p] : w[p + 1];
-        const unsigned rcv = (unsigned)__builtin_amdgcn_update_dpp(0, (int)snd, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
-        w[p] = o1 ? rcv : w[p];
-        w[p + 1] = o1 ? w[p + 1] : rcv;
-    }
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {     // exchange with lane ^ 2: pairs (w0, w2), (w1, w3)
-        const unsigned snd = o2 ? w[p] : w[p + 2];
-        const unsigned rcv = (unsigned)__builtin_amdgcn_update_dpp(0, (int)snd, 0x4E, 0xF, 0xF, false);  // quad_perm [2,3,0,1]
-        w[p] = o2 ? rcv : w[p];
-        w[p + 2] = o2 ? w[p + 2] : rcv;
-    }
-}
-
-#ifndef OZ2_LOAD_NT
-#define OZ2_LOAD_NT 1  // 0: no non-temporal operand loads anywhere.  Measured: no gain where the operands would fit the Infinity Cache (8192^2 x 256 ... 2048,
-                       // 4096^2), and -5 % of the whole call at 8192^2 x 1024, where they evict the operand planes the GEMMs are about to read
-#endif
+// Operand loads are non-temporal.  Plain loads measured: no gain where the operands would fit the Infinity Cache (8192^2 x 256 ... 2048, 4096^2), and -5 % of
+// the whole call at 8192^2 x 1024, where they evict the operand planes the GEMMs are about to read.
 // v[0..3] = x[k0 .. k0+3], zero beyond k: 16-byte loads when the four elements exist and start on a 16-byte boundary
 // NT: non-temporal (the data is read once); false where the same workgroup re-reads the row right away (two-pass bound extract: with nt
 // loads in the maxima pass the second pass went back to HBM -- ZGEMM 8192^3 bounds phase 2.58 -> 2.81 ms)
 template <typename T, bool NT = true> __device__ __forceinline__ void load4(const T* x, size_t k0, size_t k, T (&v)[4]) {
     const T* p = x + k0;
-    if (OZ2_STAGE_VLOAD && k0 + 4 <= k && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+    if (k0 + 4 <= k && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
         typedef unsigned V4 __attribute__((ext_vector_type(4)));
         constexpr int NQ = (int)(4 * sizeof(T) / 16);
         V4 r[NQ];
 #pragma unroll
-        for (int i = 0; i < NQ; ++i) r[i] = (NT && OZ2_LOAD_NT) ? __builtin_nontemporal_load((const V4*)p + i) : ((const V4*)p)[i];
+        for (int i = 0; i < NQ; ++i) r[i] = NT ? __builtin_nontemporal_load((const V4*)p + i) : ((const V4*)p)[i];
         __builtin_memcpy(v, r, sizeof(r));
     } else {
 #pragma unroll
@@ -214,31 +185,6 @@ __device__ __forceinline__ int fused_final_shift(const StageArgs& a, size_t row,
 #define OZ2_ROW_SHIFT(a_, row_, writer_)                                                                                        \
     ((a_).fin_max == nullptr ? -(int)((const int16_t*)((const char*)(a_).sft + OZ2_ZW))[(row_)] : fused_final_shift((a_), (row_), (writer_), OZ2_ZW))
 
-#ifndef OZ2_BOUND_FLOAT
-#define OZ2_BOUND_FLOAT 1
-#endif
-#ifndef OZ2_STAGE_PAIRLOAD
-#define OZ2_STAGE_PAIRLOAD 1  // row-strided kernels, 8-byte elements: two rows per lane and 16-byte load
-#endif
-#ifndef OZ2_AMAX_PREFETCH
-#define OZ2_AMAX_PREFETCH 1  // row-maximum loops keep several loads in flight per thread (experiment switch)
-#endif
-#ifndef OZ2_STAGE_KCHUNK
-#define OZ2_STAGE_KCHUNK 1  // K-major quantise: grid over (row, 1024-wide k chunk) instead of one workgroup looping over a whole row
-#endif
-#ifndef OZ2_STAGE_RTFAST
-#define OZ2_STAGE_RTFAST 1  // row-strided kernels: the row-tile index is the fast grid dimension: the workgroups in flight read whole columns (one sequential
-                           // window of the operand) and write 4 adjacent 128-byte runs per row and plane; 0 = k-tile index fastest (quantise A: 314 vs 283 us)
-#endif
-#if defined(OZ2_PRODUCT_BUILD) && defined(OZ2_PROBE_F6_NOSTORE)
-#error "OZ2_PROBE_F6_NOSTORE is a timing probe (the planes are never written): not allowed in the product build of libgemmul8.so"
-#endif
-#ifndef OZ2_F6_FLOAT_CHAIN
-#define OZ2_F6_FLOAT_CHAIN 1  // FP6 panel images: residue, split, codes and packing in fp32 (put_f6_planes_f); 0 = the integer chain of the e4m3 writer
-#endif
-#ifndef OZ2_STAGE_FLOATRES
-#define OZ2_STAGE_FLOATRES 1  // 1: residues from a two-level FLOATING-POINT reduction (below); 0: the byte-wise integer path (v_dot4_u32_u8)
-#endif
 
 // FP8 residue planes: residues up to +-544 are split into 2-3 e4m3 planes of integers <= 16 (mod.hpp:159-189, 361-410)
 __device__ __forceinline__ void put_fp8_planes(const StageArgs& a, int8_t* o, int t, const int (&rr)[4]) {
@@ -306,8 +252,8 @@ __device__ __forceinline__ size_t f6_lane_offset(const StageArgs& a, size_t row,
     return panel + inner;
 }
 
-// The same planes from residues kept as FLOATS (round 5).  The FP6 writer is VALU-bound (config 3: 3.0 ms against ~1.3 ms of memory time) and the integer
-// form spends ~20 operations per value and modulus: residue (fma, mad, add), int -> float, split (mul, rint, fma), float -> int twice, two sign-magnitude
+// The same planes from residues kept as FLOATS (round 5).  The FP6 writer is VALU-bound (config 3: 3.0 ms against ~1.3 ms of memory time) and the retired integer
+// form spent ~20 operations per value and modulus: residue (fma, mad, add), int -> float, split (mul, rint, fma), float -> int twice, two sign-magnitude
 // codes (sub, cmp, select each), shifts and ors.  Every quantity here is an integer below 2^24, so the whole chain runs in fp32 with the SAME quotients:
 //   residue  q = fma(R, RN(1/p), 1.5 * 2^23) - 1.5 * 2^23 (the very rounding of residue_from_small), r = fma(-q, p, R)              3
 //   split    squares: hi = rint(r / s), lo = fma(-s, hi, r) (fp8_split_sq);  Karatsuba: hi = copysign(ceil(|r| / 16), r), lo = fma(-16, hi, r)   3
@@ -329,11 +275,7 @@ __device__ __forceinline__ void put_f6_word_f(int8_t* o, const float (&v)[4]) {
     const unsigned nb = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0xF9, 0xF, 0xF, true);  // quad_perm [1, 2, 3, 3]
     const unsigned j = threadIdx.x & 3u;
     const unsigned d = (w >> (8u * j)) | (nb << (24u - 8u * j));
-#ifdef OZ2_PROBE_F6_NOSTORE  // timing probe: everything but the store
-    asm volatile("" ::"v"(d), "v"(o));
-#else
     if (j < 3u) *(unsigned*)o = d;
-#endif
 }
 __device__ __forceinline__ void put_f6_planes_f(const StageArgs& a, int8_t* o, int t, const float (&r)[4]) {
     float hi[4], lo[4];
@@ -358,14 +300,14 @@ __device__ __forceinline__ void put_f6_planes_f(const StageArgs& a, int8_t* o, i
 }
 
 // Quantise + all residues of four consecutive k in the FLOATING-POINT domain.  The quantise kernels are bound by VALU issue, not by HBM
-// (profiles/archive/r03_hbm_ab.txt, r03_valu_rates.txt): the integer path spends ~37 operations per element on trunc(x * 2^s) = +-M * 2^E and
+// (profiles/archive/r03_hbm_ab.txt, r03_valu_rates.txt): the byte-wise integer path (retired) spent ~37 operations per element on trunc(x * 2^s) = +-M * 2^E and
 // ~7.75 per residue (two v_dot4_u32_u8 over the bytes of M, sign correction, quotient step, packing).  Here:
 //   xs = trunc(ldexp(x, s))                       2 FP64 operations per element; exact (a power-of-two scaling, then v_trunc_f64)
 //   level 1, per PAIR of moduli, P = p_t * p_t+1:  R = fma(-rint(xs * RN(1/P)), P, xs)      3 FP64 operations per pair
 //        q = rint(..) need not be the nearest integer: R = xs - q P is formed EXACTLY by the fma (an integer below 2^53) and
 //        R == xs (mod P); |R| <= P/2 + 2 for |xs| < 2^53.  |xs| >= 2^53 (num_moduli > 15 only; wave-uniform test): |R| <= |xs| 2^-52
 //        < 2^40, and one more step of the same form brings it to |R| <= P/2 + 1.
-//   level 2, per modulus: the single-fma quotient of finish_residue on the SIGNED R (|R| < 2^20.2: exact in fp32):
+//   level 2, per modulus: a single-fma quotient on the SIGNED R (|R| < 2^20.2: exact in fp32):
 //        qf = fma(float(R), RN(1/p), 1.5 * 2^23) rounds to 1.5 * 2^23 + q, q = rint(R / p) exactly (|R| * |RN(1/p) - 1/p| < 2^-4.9 / p
 //        stays clear of the 1/(2p) tie distance of an odd p; p = 256 / 1024: a tie gives +-p/2, the same byte / fixed below);
 //        its low 24 bits are 2^22 + q, so v_mad_i32_i24(bits, -p, R) = (R - q p) - p 2^22: the canonical residue in the low byte,
@@ -400,65 +342,6 @@ template <typename T> __device__ __forceinline__ void emit4_mod_float(const Stag
         }
     }
     auto run = [&]<bool WIDE, bool BIG>() {
-        if constexpr (!WIDE && OZ2_STAGE_V16) {
-            // experiment (see OZ2_STAGE_V16): four planes per trip, quad-transposed so that lane q stores the 16 bytes of plane t + q
-            typedef unsigned V4 __attribute__((ext_vector_type(4)));
-            const unsigned q = threadIdx.x & 3u;
-            int8_t* oq = out - 4 * q;
-            auto pack = [](const int (&r)[4]) {
-                return ((unsigned)r[0] & 0xFFu) | (((unsigned)r[1] & 0xFFu) << 8) | (((unsigned)r[2] & 0xFFu) << 16) | ((unsigned)r[3] << 24);
-            };
-            for (int t = a.t_begin; t < a.t_end; t += 4) {
-                unsigned wr[4] = {0u, 0u, 0u, 0u}, wi[4] = {0u, 0u, 0u, 0u}, ws[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int tp = t + 2 * h;
-                    if (tp >= a.t_end) break;
-                    const double P = a.pairP[(tp - a.t_begin) >> 1], invP = a.pairInvP[(tp - a.t_begin) >> 1];
-                    int Rr[4], Ri[4];
-                    float Fr[4], Fi[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        double R = fma(-rint(xr[e] * invP), P, xr[e]);
-                        if constexpr (BIG) R = fma(-rint(R * invP), P, R);
-                        Rr[e] = (int)R, Fr[e] = (float)R;
-                        if constexpr (E::cplx) {
-                            double I = fma(-rint(xi[e] * invP), P, xi[e]);
-                            if constexpr (BIG) I = fma(-rint(I * invP), P, I);
-                            Ri[e] = (int)I, Fi[e] = (float)I;
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const int tt = tp + u;
-                        if (tt >= a.t_end) break;
-                        const ModConst mc = a.mt.mc[tt];
-                        int rr[4], ri[4], rs[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            rr[e] = residue_from_small<false>(Rr[e], Fr[e], mc);
-                            if constexpr (E::cplx) {
-                                ri[e] = residue_from_small<false>(Ri[e], Fi[e], mc);
-                                rs[e] = wrapping((int)(int8_t)rr[e] + (int)(int8_t)ri[e], mc.p);
-                            }
-                        }
-                        wr[2 * h + u] = pack(rr);
-                        if constexpr (E::cplx) wi[2 * h + u] = pack(ri), ws[2 * h + u] = pack(rs);
-                    }
-                }
-                quad_transpose4(wr, q);
-                if constexpr (E::cplx) quad_transpose4(wi, q), quad_transpose4(ws, q);
-                if (t + (int)q < a.t_end) {
-                    int8_t* o = oq + (size_t)(t + (int)q) * a.plane_stride;
-                    *(V4*)o = V4{wr[0], wr[1], wr[2], wr[3]};
-                    if constexpr (E::cplx) {
-                        *(V4*)(o + a.part_stride) = V4{wi[0], wi[1], wi[2], wi[3]};
-                        *(V4*)(o + 2 * a.part_stride) = V4{ws[0], ws[1], ws[2], ws[3]};
-                    }
-                }
-            }
-            return;
-        }
         for (int t = a.t_begin; t < a.t_end; t += 2) {
             const double P = a.pairP[(t - a.t_begin) >> 1], invP = a.pairInvP[(t - a.t_begin) >> 1];
             int Rr[4], Ri[4];
@@ -479,7 +362,7 @@ template <typename T> __device__ __forceinline__ void emit4_mod_float(const Stag
                 const int tt = t + u;
                 if (tt >= a.t_end) break;
                 const ModConst mc = a.mt.mc[tt];
-                if constexpr (WIDE && OZ2_F6_FLOAT_CHAIN) {
+                if constexpr (WIDE) {
                     if (a.f6) {  // (uniform) FP6 panel images from float residues: see put_f6_planes_f
                         const float pf = (float)mc.p, hf = (float)(mc.p >> 1);
                         float fr[4], fi[4], fs[4];
@@ -508,7 +391,8 @@ template <typename T> __device__ __forceinline__ void emit4_mod_float(const Stag
                 }
                 if constexpr (WIDE) {
                     int8_t* o = out + (size_t)(tt < 6 ? 2 * tt : 12 + 3 * (tt - 6)) * a.plane_stride;
-                    if (a.f6) {  // (uniform) FP6 panel images: `out` is this lane's dword address inside plane 0
+                    if (a.f6) {  // never taken: FP6 panel images left through the float chain above.  The compiler drops the branch; the source keeps it because
+                                 // deleting it renumbers basic blocks in the assembly listing, and the switch retirement was held to byte-identical listings
                         put_f6_planes(a, o, tt, rr);
                         if constexpr (E::cplx) {
                             put_f6_planes(a, o + a.part_stride, tt, ri);
@@ -588,8 +472,8 @@ __device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0,
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             // ceil(|x| * 2^s) in FP64 (v_ldexp_f64, v_ceil_f64, v_cvt_i32_f64: exact, the value is below 2^7 by construction of s) instead of
-            // the ~25 integer operations of upper_bound_i8 (kept in oz2_device.hpp; -DOZ2_BOUND_FLOAT=0)
-            auto ub = [&](double x) { return OZ2_BOUND_FLOAT ? (int)ceil(ldexp(fabs(x), s)) : upper_bound_i8(x, s); };
+            // the ~25 integer operations of the bit-field form
+            auto ub = [&](double x) { return (int)ceil(ldexp(fabs(x), s)); };
             const int br = ub(E::re(v[e]));
             wr |= ((unsigned)br & 0xFFu) << (8 * e);
             if constexpr (E::cplx) {
@@ -603,127 +487,8 @@ __device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0,
             *(unsigned*)(out + a.part_stride) = wi;
             *(unsigned*)(out + 2 * a.part_stride) = wd;
         }
-    } else if constexpr (OZ2_STAGE_FLOATRES) {
-        emit4_mod_float<T>(a, out, v, s);
     } else {
-        uint64_t Mr[4], Mi[4];
-        int Er[4], Ei[4];
-        bool nr[4], ni[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const ScaledInt x = trunc_scale(E::re(v[e]), s);
-            Mr[e] = x.M;
-            Er[e] = x.E;
-            nr[e] = x.neg;
-            if constexpr (E::cplx) {
-                const ScaledInt y = trunc_scale(E::im(v[e]), s);
-                Mi[e] = y.M;
-                Ei[e] = y.E;
-                ni[e] = (a.conj && y.M != 0) ? !y.neg : y.neg;  // a zero stays +0 (two's-complement residue path)
-            }
-        }
-        // E > 0 (|x|*2^s >= 2^53) cannot happen for num_moduli <= 15; one wave-uniform test keeps it out of the common path
-        bool anyE = false;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            anyE |= Er[e] > 0;
-            if constexpr (E::cplx) anyE |= Ei[e] > 0;
-        }
-        const bool fastE = !__any(anyE);
-        unsigned rlo[4], rhi[4], ilo[4], ihi[4];  // fastE: M or its 56-bit two's complement
-        Bytes128 Xr[4], Xi[4];                    // otherwise: M*2^E or its 120-bit two's complement
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (fastE) {
-                const uint64_t mt = nr[e] ? (1ull << 56) - Mr[e] : Mr[e];
-                rlo[e] = (unsigned)mt, rhi[e] = (unsigned)(mt >> 32);
-                if constexpr (E::cplx) {
-                    const uint64_t it = ni[e] ? (1ull << 56) - Mi[e] : Mi[e];
-                    ilo[e] = (unsigned)it, ihi[e] = (unsigned)(it >> 32);
-                }
-            } else {
-                Xr[e] = shifted_bytes(Mr[e], Er[e], nr[e]);
-                if constexpr (E::cplx) Xi[e] = shifted_bytes(Mi[e], Ei[e], ni[e]);
-            }
-        }
-        auto put_fp8 = [&](int8_t* o, int t, const int (&rr)[4]) {
-            if (a.f6) put_f6_planes(a, o, t, rr);
-            else put_fp8_planes(a, o, t, rr);
-        };
-        // one pass over the moduli; FAST / WIDE are compile-time so the residue code is branch-free.  Complex: the residues of
-        // Re, Im and wrapping(Re + Im) go to the three parts (INT8: the sum of the int8-cast values, mod.hpp:321-325).
-        auto planes = [&]<bool FAST, bool WIDE>() {
-            auto residues = [&](int t, int (&rr)[4], int (&ri)[4], int (&rs)[4]) {
-                const ModConst mc = a.mt.mc[t];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    rr[e] = FAST ? residue_sym_bytes_e0<WIDE>(rlo[e], rhi[e], nr[e], mc) : residue_sym_bytes128<WIDE>(Xr[e], nr[e], mc);
-                    if constexpr (E::cplx) {
-                        ri[e] = FAST ? residue_sym_bytes_e0<WIDE>(ilo[e], ihi[e], ni[e], mc) : residue_sym_bytes128<WIDE>(Xi[e], ni[e], mc);
-                        rs[e] = WIDE ? wrapping(rr[e] + ri[e], mc.p) : wrapping((int)(int8_t)rr[e] + (int)(int8_t)ri[e], mc.p);
-                    }
-                }
-            };
-            auto pack = [](const int (&r)[4]) {
-                return ((unsigned)r[0] & 0xFFu) | (((unsigned)r[1] & 0xFFu) << 8) | (((unsigned)r[2] & 0xFFu) << 16) | ((unsigned)r[3] << 24);
-            };
-            if constexpr (!WIDE && OZ2_STAGE_V16) {
-                // four planes per trip; the dwords of a lane quad (16 consecutive k of this row) are transposed so that lane q stores the
-                // 16 bytes of plane t + q: 256 contiguous bytes per plane and store instruction, a quarter of the store instructions
-                typedef unsigned V4 __attribute__((ext_vector_type(4)));
-                const unsigned q = threadIdx.x & 3u;
-                int8_t* oq = out - 4 * q;  // first byte of the quad's 16-byte run
-                for (int t = a.t_begin; t < a.t_end; t += 4) {
-                    unsigned wr[4] = {0u, 0u, 0u, 0u}, wi[4] = {0u, 0u, 0u, 0u}, ws[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (t + i < a.t_end) {
-                            int rr[4], ri[4], rs[4];
-                            residues(t + i, rr, ri, rs);
-                            wr[i] = pack(rr);
-                            if constexpr (E::cplx) wi[i] = pack(ri), ws[i] = pack(rs);
-                        }
-                    }
-                    quad_transpose4(wr, q);
-                    if constexpr (E::cplx) quad_transpose4(wi, q), quad_transpose4(ws, q);
-                    if (t + (int)q < a.t_end) {
-                        int8_t* o = oq + (size_t)(t + (int)q) * a.plane_stride;
-                        *(V4*)o = V4{wr[0], wr[1], wr[2], wr[3]};
-                        if constexpr (E::cplx) {
-                            *(V4*)(o + a.part_stride) = V4{wi[0], wi[1], wi[2], wi[3]};
-                            *(V4*)(o + 2 * a.part_stride) = V4{ws[0], ws[1], ws[2], ws[3]};
-                        }
-                    }
-                }
-                return;
-            }
-            for (int t = a.t_begin; t < a.t_end; ++t) {
-                int rr[4], ri[4], rs[4];
-                residues(t, rr, ri, rs);
-                if constexpr (WIDE) {
-                    int8_t* o = out + (size_t)(t < 6 ? 2 * t : 12 + 3 * (t - 6)) * a.plane_stride;
-                    put_fp8(o, t, rr);
-                    if constexpr (E::cplx) {
-                        put_fp8(o + a.part_stride, t, ri);
-                        put_fp8(o + 2 * a.part_stride, t, rs);
-                    }
-                } else {
-                    int8_t* o = out + (size_t)t * a.plane_stride;
-                    *(unsigned*)o = pack(rr);
-                    if constexpr (E::cplx) {
-                        *(unsigned*)(o + a.part_stride) = pack(ri);
-                        *(unsigned*)(o + 2 * a.part_stride) = pack(rs);
-                    }
-                }
-            }
-        };
-        if (a.backend == kFP8) {
-            if (fastE) planes.template operator()<true, true>();
-            else planes.template operator()<false, true>();
-        } else {
-            if (fastE) planes.template operator()<true, false>();
-            else planes.template operator()<false, false>();
-        }
+        emit4_mod_float<T>(a, out, v, s);
     }
 }
 
@@ -750,7 +515,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
             return;
         }
     }
-    if constexpr (MODE == MODE_MOD && OZ2_STAGE_KCHUNK && sizeof(T) <= 8) {  // (16-byte elements measured 4 % better with the row loop)
+    if constexpr (MODE == MODE_MOD && sizeof(T) <= 8) {  // (16-byte elements measured 4 % better with the row loop)
         // quantise: one workgroup per 1024-wide k chunk of a row, the chunk index fastest: the workgroups in flight walk through
         // memory together (one row after the other) instead of streaming ~2000 rows at once
         const unsigned nch = (unsigned)(a.kp / 1024 + (a.kp % 1024 != 0));
@@ -805,13 +570,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
             return;
         }
         U am = 0;
-        for (size_t kk = threadIdx.x; !OZ2_AMAX_PREFETCH && kk < a.k; kk += 256) {
-            const T v = x[kk];
-            const U ar = (U)fabs(E::re(v)), ai = (U)fabs(E::im(v));
-            am = ar > am ? ar : am;
-            am = ai > am ? ai : am;
-        }
-        for (size_t k0 = (size_t)threadIdx.x * 4; OZ2_AMAX_PREFETCH && k0 < a.k; k0 += 2048) {  // two 4-element groups in flight per thread
+        for (size_t k0 = (size_t)threadIdx.x * 4; k0 < a.k; k0 += 2048) {  // two 4-element groups in flight per thread
             T v0[4], v1[4];
             load4<T, false>(x, k0, a.k, v0);
             load4<T, false>(x, k0 + 1024 < a.k ? k0 + 1024 : k0, a.k, v1);
@@ -846,19 +605,17 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
     }
 }
 
-// Row-strided operand: 1-D grid of ceil(kp/TK) * ceil(rows/TR) workgroups, the k-tile index fastest (a 2-D grid would cap the
+// Row-strided operand: 1-D grid of ceil(kp/TK) * ceil(rows/TR) workgroups, the row-tile index fastest (a 2-D grid would cap the
 // row-tile count at 65535, i.e. operands of ~1M rows); 256 threads; tile TR rows x TK k staged RAW in LDS
 template <typename T> struct StageTile {
-    // 16.6 KiB of LDS per workgroup for every type (8 workgroups per CU): 32 rows of float, 16 rows of the 8- and 16-byte
-    // types (a 16-row read segment of doubles is still one full 128-B cache line)
+    // 16.6 KiB of LDS per workgroup for every type (8 workgroups per CU): 32 rows x 128 k of float, 16 rows x 128 k of the 8-byte types (a 16-row read
+    // segment of doubles is still one full 128-B cache line), 8 rows x 128 k of the 16-byte types (128-byte runs per row and plane on the way out; 16 rows x
+    // 64 k = 64-byte runs measured slower)
 #ifndef OZ2_STAGE_TR8
-#define OZ2_STAGE_TR8 16  // rows per tile of the 8- and 16-byte element types
+#define OZ2_STAGE_TR8 16  // rows per tile of the 8-byte element types
 #endif
-#ifndef OZ2_STAGE_Z_WIDE
-#define OZ2_STAGE_Z_WIDE 1  // 16-byte elements: 8 rows x 128 k (128-byte runs per row and plane on the way out) instead of 16 rows x 64 k (64-byte runs)
-#endif
-    static constexpr int TR = sizeof(T) == 4 ? 32 : (sizeof(T) == 16 && OZ2_STAGE_Z_WIDE) ? 8 : OZ2_STAGE_TR8;
-    static constexpr int TK = (sizeof(T) == 16 && !OZ2_STAGE_Z_WIDE) ? 64 : 128;
+    static constexpr int TR = sizeof(T) == 4 ? 32 : sizeof(T) == 16 ? 8 : OZ2_STAGE_TR8;
+    static constexpr int TK = 128;
 };
 template <typename T, int MODE>
 __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const unsigned bid) {
@@ -871,13 +628,10 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
     __shared__ __attribute__((aligned(16))) T tile[TR][PITCH];
     using UBm = typename std::conditional<sizeof(U) == 8, unsigned long long, unsigned>::type;
     [[maybe_unused]] __shared__ UBm rowam[TR];
-#if OZ2_STAGE_RTFAST
+    // the row-tile index is the fast grid dimension: the workgroups in flight read whole columns (one sequential window of the operand) and write 4 adjacent
+    // 128-byte runs per row and plane (k-tile index fastest: quantise A 314 vs 283 us)
     const unsigned nrt = (unsigned)((a.rows + TR - 1) / TR);
     const unsigned kt = bid / nrt, rt = bid - kt * nrt;
-#else
-    const unsigned nkt = (unsigned)(a.kp / TK);
-    const unsigned rt = bid / nkt, kt = bid - rt * nkt;
-#endif
     const size_t r0 = (size_t)rt * TR;
     const size_t kb = (size_t)kt * TK;
     if constexpr (MODE == MODE_BOUND) {
@@ -900,7 +654,7 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
         }
         if (pp == 0) rowam[rr] = v;
     }
-    if constexpr (OZ2_STAGE_PAIRLOAD && sizeof(T) <= 8) {
+    if constexpr (sizeof(T) <= 8) {
         // 4- and 8-byte elements: a lane fetches RPL = 4 / 2 consecutive rows with one 16-byte load (a half / a quarter of the load
         // instructions, 1 KiB per wave instruction) when the rows exist and the group is 16-byte aligned; all loads of the tile are in
         // flight at once.  (float operands took the one-element-per-lane path until round 3: quantise A 222 us = 3.3 TB/s at 8192^2,
@@ -920,7 +674,7 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
             V4 v = {0u, 0u, 0u, 0u};
             if (kg < a.k) {
                 if (pair_ok) {
-                    v = OZ2_LOAD_NT ? __builtin_nontemporal_load((const V4*)(x + kg * a.ld)) : *(const V4*)(x + kg * a.ld);
+                    v = __builtin_nontemporal_load((const V4*)(x + kg * a.ld));
                 } else {
 #pragma unroll
                     for (int e = 0; e < RPL; ++e) {
@@ -1019,11 +773,9 @@ static_assert(2 * sizeof(StageArgs) + 16 <= 4096, "two argument blocks must fit 
 //     transposed through a wave-private LDS tile (row pitch 144 bytes: conflict-free 16-byte reads), 128 bytes of every row at a time.
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef unsigned v6u __attribute__((ext_vector_type(6)));
-#ifndef OZ2_F6_LANE_KERNEL
-#define OZ2_F6_LANE_KERNEL 1  // 0: real FP6 planes through the generic stage kernels (four k per lane), as complex operands.  (A complex form was built in
-                              // round 5 -- the fragment in two halves of 16 k, three plane sets per value -- and needs 282-314 registers: the 16-float operand
-                              // tuples of the pack instruction with half their lanes as padding fragment the register file; one wave per SIMD: not kept.)
-#endif
+// (Complex operands take the generic stage kernels, four k per lane.  A complex form of this kernel was built in round 5 -- the fragment in two halves of 16 k,
+// three plane sets per value -- and needs 282-314 registers: the 16-float operand tuples of the pack instruction with half their lanes as padding fragment
+// the register file; one wave per SIMD: not kept.)
 template <typename T> __device__ __forceinline__ void stage_f6_body(const StageArgs& a, const unsigned bid, const bool kmajor, char* tile /* this wave's 64 x 144 bytes */) {
     static_assert(!ET<T>::cplx, "real operands");
     constexpr int EPL = 16 / (int)sizeof(T);   // elements per 16-byte piece
@@ -1049,7 +801,7 @@ template <typename T> __device__ __forceinline__ void stage_f6_body(const StageA
                 V4 t = {0u, 0u, 0u, 0u};
                 if (r < a.rows) {
                     if (kk + EPL <= a.k && (reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
-                        t = OZ2_LOAD_NT ? __builtin_nontemporal_load((const V4*)src) : *(const V4*)src;
+                        t = __builtin_nontemporal_load((const V4*)src);
                     } else {
                         T e[EPL];
 #pragma unroll
@@ -1074,7 +826,7 @@ template <typename T> __device__ __forceinline__ void stage_f6_body(const StageA
 #pragma unroll
         for (int kk = 0; kk < 32; ++kk) {
             const size_t kg = k0 + kk;
-            v[kk] = (row < a.rows && kg < a.k) ? (OZ2_LOAD_NT ? __builtin_nontemporal_load(src + kg * a.ld) : src[kg * a.ld]) : ET<T>::zero();
+            v[kk] = (row < a.rows && kg < a.k) ? __builtin_nontemporal_load(src + kg * a.ld) : ET<T>::zero();
         }
     }
     if (row >= a.rows) return;
@@ -1192,12 +944,7 @@ template <typename T> __device__ __forceinline__ void stage_f6_body(const StageA
     if (__any(big)) run.template operator()<true>();
     else run.template operator()<false>();
 }
-#ifdef OZ2_F6_WAVES  // experiment: force the register budget of that many waves per SIMD
-#define OZ2_F6_KATTR __attribute__((amdgpu_waves_per_eu(OZ2_F6_WAVES, OZ2_F6_WAVES)))
-#else
-#define OZ2_F6_KATTR
-#endif
-template <typename T> __global__ void __launch_bounds__(256) OZ2_F6_KATTR quantise_f6_pair_kernel(const StageArgs a, const StageArgs b, const unsigned nA, const int kmA, const int kmB) {
+template <typename T> __global__ void __launch_bounds__(256) quantise_f6_pair_kernel(const StageArgs a, const StageArgs b, const unsigned nA, const int kmA, const int kmB) {
     __shared__ __attribute__((aligned(16))) char tile[4][64 * 144];
     char* const mine = tile[threadIdx.x >> 6];
     if (blockIdx.x < nA) stage_f6_body<T>(a, blockIdx.x, kmA != 0, mine);
@@ -1223,7 +970,7 @@ template <typename T> __device__ __forceinline__ void amax_strided_body(const Am
     const size_t rows = o.rows, ld = o.ld;
     // a lane owns RPL consecutive rows = 16 bytes of a column (one 16-byte load when they exist and are aligned); 64 rows per workgroup,
     // the remaining lanes spread over KL k-lanes
-    constexpr int RPL = OZ2_STAGE_PAIRLOAD ? 16 / (int)sizeof(T) : 1;
+    constexpr int RPL = 16 / (int)sizeof(T);
     constexpr int LPC = 64 / RPL, KL = 256 / LPC;
     __shared__ U sm[KL][64];
     const int rl = threadIdx.x % LPC, ky = threadIdx.x / LPC;
@@ -1244,7 +991,7 @@ template <typename T> __device__ __forceinline__ void amax_strided_body(const Am
         size_t kk = kbeg + ky;
         if (vec) {
             typedef unsigned V4 __attribute__((ext_vector_type(4)));
-            for (; OZ2_AMAX_PREFETCH && kk + 3 * KL < kend; kk += 4 * KL) {  // four strided 16-byte loads in flight per thread
+            for (; kk + 3 * KL < kend; kk += 4 * KL) {  // four strided 16-byte loads in flight per thread
                 V4 raw[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) raw[u] = *(const V4*)(x + (kk + (size_t)KL * u) * ld);
@@ -1292,11 +1039,11 @@ template <typename T> __global__ void __launch_bounds__(256) amax_pair_kernel(co
 template <typename T, int MODE> static size_t stage_blocks(bool kmajor, const StageArgs& a) {
     if (a.rows == 0) return 0;
     if (kmajor && MODE == MODE_MOD && a.f6) return ((a.rows + 7) / 8) * (a.kp / 128);
-    if (kmajor) return a.rows * ((MODE == MODE_MOD && OZ2_STAGE_KCHUNK && sizeof(T) <= 8) ? (a.kp + 1023) / 1024 : 1);
+    if (kmajor) return a.rows * ((MODE == MODE_MOD && sizeof(T) <= 8) ? (a.kp + 1023) / 1024 : 1);
     return (a.kp / StageTile<T>::TK) * ((a.rows + StageTile<T>::TR - 1) / StageTile<T>::TR);
 }
 template <typename T> static hipError_t launch_quantise_stage(hipStream_t stream, bool kmA, const StageArgs& a, bool kmB, const StageArgs& b) {
-    if constexpr (OZ2_F6_LANE_KERNEL && !ET<T>::cplx) {
+    if constexpr (!ET<T>::cplx) {
         // real operands, FP6 panel images on both sides (an operand that is skipped has no rows): one lane per fragment
         if ((a.rows == 0 || a.f6) && (b.rows == 0 || b.f6) && (a.rows != 0 || b.rows != 0) && (a.rows ? a.backend : b.backend) == kFP8) {
             const size_t nA = a.rows ? ((a.rows + 63) / 64) * (a.kp / 128) : 0, nB = b.rows ? ((b.rows + 63) / 64) * (b.kp / 128) : 0;

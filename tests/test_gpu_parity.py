@@ -409,7 +409,7 @@ def test_complex_bound_one_or_two_launches(dtype, tile, launches, monkeypatch):
 def test_epilogue_reduction_on_extreme_accumulators(k):
     """The requantise epilogue on accumulators AT the bounds the residue planes allow (planes of +-127 with long runs of equal sign, so
     |sum| reaches k * 127^2), fed straight to gemmul8_lowprec_gemm: K <= 512 takes the three-instruction form (exact below 2^23; k = 256 also
-    runs a row of -128 x -128 = the 2^22 bound of the float-pattern form that -DOZ2_MOD256=1 builds use there),
+    runs a row of -128 x -128 = the 2^22 bound of the float-pattern form that -DOZ2_MOD256=1 builds used there: retired, 853556f),
     longer K the byte-dot form on biased accumulators (any int32).  Random operands never come near these values; the expected residues
     are plain integer arithmetic."""
     import ctypes as C
@@ -430,7 +430,7 @@ def test_epilogue_reduction_on_extreme_accumulators(k):
         x[:, 1, :] = -127
         x[:, 2, ::2] = 127
         if k == 256:
-            x[:, 3, :] = -128                 # 256 * 128^2 = 2^22: the bound of the float-pattern form (RED_MAGIC, -DOZ2_MOD256=1 builds)
+            x[:, 3, :] = -128                 # 256 * 128^2 = 2^22: the bound of the float-pattern form (RED_MAGIC; its -DOZ2_MOD256=1 builds are retired, 853556f)
         out = np.zeros((N, rows_pad, k), dtype=np.int8)
         out[:, :rows] = x
         return x, out

@@ -67,7 +67,7 @@ def _mfma_blocks(blocks):
 
 def test_int8_kernels_registers_and_scratch(i8):
     ks = {n: v for n, v in i8.items() if "gemm_i8_kernel" in n}
-    assert len(ks) == 7, sorted(ks)   # MOD / CPLX x {K-step barrier small-K, K-step barrier, ping-pong} + the bound GEMM (a -DOZ2_MOD256=1 build adds EPI_MOD256)
+    assert len(ks) == 7, sorted(ks)   # MOD / CPLX x {K-step barrier small-K, K-step barrier, ping-pong} + the bound GEMM (the -DOZ2_MOD256=1 build that added EPI_MOD256 is retired, 853556f)
     for n, (vg, sc, blocks) in ks.items():
         assert vg <= 168, (n, vg)     # 12 waves per CU = 3 per SIMD
         residue = "ILi0E" in n or "ILi2E" in n or "ILi3E" in n

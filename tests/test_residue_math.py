@@ -1,5 +1,5 @@
 """CPU model of the floating-point residue reductions used by the GEMM epilogues and the quantise kernels (oz2_device.hpp:
-mod_i32_sym_odd_f64, mod_small_sym_odd, residue_sym_bytes*) checked against exact integer arithmetic.  numpy float32 / float64
+mod_i32_sym_odd_f64, mod_small_sym_odd; residue_sym_bytes*: retired, 853556f) checked against exact integer arithmetic.  numpy float32 / float64
 multiply, rint and fma-free differences are the same IEEE operations the kernels are compiled to (-ffp-contract=off)."""
 import numpy as np
 import pytest
@@ -156,7 +156,7 @@ def test_one_step_small(p):
 
 @pytest.mark.parametrize("p", INT8_MODULI)
 def test_byte_dot_residue(p):
-    """oz2_device.hpp residue_sym_bytes: sum_i byte_i(M) * (256^i mod p), one fp32 quotient step, sign applied last."""
+    """residue_sym_bytes (retired device code): sum_i byte_i(M) * (256^i mod p), one fp32 quotient step, sign applied last."""
     rng = np.random.default_rng(1000 + p)
     M = np.concatenate([rng.integers(0, 2 ** 53, size=400_000, dtype=np.int64), np.arange(0, 70_000, dtype=np.int64),
                         (2 ** 53 - 1 - np.arange(0, 1000)).astype(np.int64),
@@ -180,7 +180,7 @@ def test_byte_dot_residue(p):
 
 @pytest.mark.parametrize("p", INT8_MODULI)
 def test_byte_dot_residue_signed_fma(p):
-    """oz2_device.hpp residue_sym_bytes_e0: bytes of M or of the 56-bit two's complement 2^56 - M (negative values) plus
+    """residue_sym_bytes_e0 (retired, 853556f:gemmul8_amd/csrc/oz2_device.hpp): bytes of M or of the 56-bit two's complement 2^56 - M (negative values) plus
     k56 = (-2^56 mod p); quotient from one fma(float(s), 1/p, 2^23) whose low 24 bits are rint(s/p)."""
     rng = np.random.default_rng(2000 + p)
     M = np.concatenate([rng.integers(1, 2 ** 53, size=300_000, dtype=np.int64), np.arange(1, 70_000, dtype=np.int64),
@@ -208,7 +208,7 @@ def test_byte_dot_residue_signed_fma(p):
 
 @pytest.mark.parametrize("p", INT8_MODULI)
 def test_byte_dot_residue_shifted_120bit(p):
-    """oz2_device.hpp shifted_bytes + residue_sym_bytes128: bytes of M*2^E (E < 64) or of 2^120 - M*2^E, four dot4, one fma."""
+    """shifted_bytes + residue_sym_bytes128 (retired, 853556f:gemmul8_amd/csrc/oz2_device.hpp): bytes of M*2^E (E < 64) or of 2^120 - M*2^E, four dot4, one fma."""
     rng = np.random.default_rng(3000 + p)
     c = [pow(256, i, p) for i in range(15)]
     k120 = (p - pow(2, 120, p)) % p
