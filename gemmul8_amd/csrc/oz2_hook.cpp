@@ -1,32 +1,48 @@
-// LD_PRELOAD hipBLAS hook: hipblas{S,D,C,Z}gemm, hipblasGemmEx, their strided-batched forms, hipblasLtMatmul and hipblasDestroy are intercepted
-// and routed to the Ozaki-II emulation (C ABI, gemmul8_c.h) according to the GEMMUL8_* environment
-// variables; everything else -- and every call the environment does not select -- is passed to the
-// real library found with dlsym(RTLD_NEXT).
+// Drop-in hipBLAS / hipBLASLt / rocBLAS hook (LD_PRELOAD): the GEMM entry points below are interposed and routed to the Ozaki-II emulation
+// (C ABI, gemmul8_c.h) according to the GEMMUL8_* environment variables; every call the environment does not select, and every call outside
+// what the emulator accepts, goes to the real routine: the next definition in the search order, or the library's already-mapped copy (real()).
+// One translation unit without kernels; it calls no BLAS routine itself.  Built twice: into libgemmul8.so, and with -DOZ2_HOOK_SHIM as
+// libgemmul8_preload.so (see abi()).
 //
-// Behavioural contract restated from the reference (GEMMul8/src/hook.cu, README.md:283-385):
-//   env (read on EVERY call unless noted)     hook.cu:170-227,284-310
-//     GEMMUL8_BACKEND          0|INT8 (default) / 1|FP8
-//     GEMMUL8_NUM_MOD_{D,S,Z,C} emulate when 2 <= N <= 20 (D,Z) / 13 (S,C); otherwise native
-//     GEMMUL8_FASTMODE_{D,S,Z,C} "1" = fast mode, default accurate
-//     GEMMUL8_SKIP_SCALE_{A,B}  "1" = keep quantised operand + shifts between calls (pointer identity)
-//     GEMMUL8_MAX_{M,N,K}, GEMMUL8_MAX_NUM_MOD, GEMMUL8_MAXWS_BACKEND (read once): workspace
-//       pre-sizing applied when a SKIP_SCALE switch is on                      hook.cu:232-281,656-662
-//   early outs: m|n|k <= 0 -> SUCCESS, null A/B/C -> INVALID_VALUE            hook.cu:616-617
-//   GEMMUL8_DIST (this build only)  blocks | moduli | fp64sum: shard every emulated GEMM over the ranks of an SPMD job (see try_dist)
-//   GEMMUL8_MIN_FLOPS (this build only) UNSET or 0 = emulate every selected call (the reference's behaviour, hook.cu:600-660);
-//                     "auto" = a fitted cost model decides per call whether the emulation wins (below_floor); a number = calls with
-//                     2*m*n*k below it use the native routine.  The first call a floor hands to the native routine is logged once.
-//   per-handle state under a mutex: three grow-only stream-ordered buffers (hipMallocAsync /
-//   hipFreeAsync), event hand-off when the handle's stream changes, skip-scaling cache
-//   (hook.cu:70-162,331-374,684-727); hipblasDestroy frees the state first (hook.cu:846-856).
-//   GEMMUL8_HOOK_ROCBLAS=1 (this build only) also intercept rocblas_{s,d,c,z}gemm, their strided-batched forms and rocblas_gemm_ex: callers
-//                     that use rocBLAS directly (HPL-style codes) -- NOT rocSOLVER, whose factorizations call rocBLAS's internal C++ templates
-//                     (INTEGRATION.md "What the hook reaches")
-//   GEMMUL8_HOOK_STATS=1 print at exit how many GEMM calls / flops were emulated and how many went to the native routines
-// This file has no kernels and calls no BLAS routine itself.
+// Interposed symbols                                                       beyond the reference (src/hook.cu:846-1055)?
+//   hipblas{S,D,C,Z}gemm, hipblasGemmEx, hipblasDestroy                     no: m|n|k <= 0 -> SUCCESS, null A/B/C -> INVALID_VALUE (hook.cu:616-617)
+//   hipblas{S,D,C,Z}gemm_64, hipblasGemmEx_64,                              yes (ROCm 7 ILP64 / WithFlags twins): the same contract; emulated when every
+//     hipblasGemmExWithFlags, hipblasGemmExWithFlags_64                       dimension fits an int, native otherwise
+//   hipblas{S,D,C,Z}gemmStridedBatched, hipblasGemmStridedBatchedEx         yes (torch.bmm): no early out, degenerate calls are the native routine's
+//   hipblasLtMatmul, hipblasLtDestroy                                       yes (PyTorch's float32 matmuls): the plain case only, see lt_try
+//   hipblasLtMatrixLayoutCreate / SetAttribute / Destroy                    yes: record what a layout holds (hipBLASLt cannot be asked)
+//   rocblas_{s,d,c,z}gemm, rocblas_{s,d,c,z}gemm_strided_batched,           yes, only with GEMMUL8_HOOK_ROCBLAS=1: applications that call rocBLAS directly
+//     rocblas_gemm_ex (in-place form), rocblas_destroy_handle                 (HPL-style codes)
+//   rocblas_internal_gemm_template<T> / _64<T>, T = float, double,          yes, only with GEMMUL8_HOOK_ROCBLAS=1 and a tested rocBLAS release: rocSOLVER's
+//     rocblas_complex_num<float / double> (eight mangled names)               trailing updates (INTEGRATION.md "What the hook reaches")
+//   gemmul8_hook_would_emulate, gemmul8_hook_rocblas_version_tested         this project's own queries (no interposition)
+//
+// Environment                      read        meaning                                                      hook.cu:170-227,232-310
+//   GEMMUL8_NUM_MOD_{S,D,C,Z}      per call    emulate when 2 <= N <= 13 (S,C) / 20 (D,Z); otherwise native
+//   GEMMUL8_FASTMODE_{S,D,C,Z}     per call    "1" = fast mode, default accurate
+//   GEMMUL8_BACKEND                per call    0|INT8 (default) / 1|FP8
+//   GEMMUL8_SKIP_SCALE_{A,B}       per call    "1" = keep the quantised operand + shifts between calls (pointer identity)
+//   GEMMUL8_MAX_{M,N,K}, GEMMUL8_MAX_NUM_MOD, GEMMUL8_MAXWS_BACKEND
+//                                  once        workspace pre-sizing, applied when a SKIP_SCALE switch is on (hook.cu:232-281,656-662)
+//  the rest is this build's only:
+//   GEMMUL8_FP8_BOUND, GEMMUL8_NONFINITE
+//                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace)
+//   GEMMUL8_MIN_FLOPS              per call    unset or 0 = emulate every selected call (the reference's behaviour); `auto` = a fitted cost model decides
+//                                              per call (below_floor); a number = floor on 2*m*n*k.  The first call a floor declines is logged once.
+//   GEMMUL8_DIST                   per call    blocks | moduli | fp64sum: shard every emulated GEMM over the ranks of an SPMD job (try_dist)
+//   GEMMUL8_BATCH_FUSED, GEMMUL8_BATCH_WORKSPACE_MB, GEMMUL8_BATCH_STREAMS
+//                                  per call    strided batches: one set of launches (default) in chunks of the given size, or lanes (emulate_batch)
+//   GEMMUL8_HOOK_ROCBLAS           per call    "1" = the rocBLAS entry points above act
+//   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
+//   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call)
+//   GEMMUL8_HOOK_VERBOSE           per call    "1" = say why a hipblasLtMatmul call was left to the native routine
+//
+// Per-handle state under a mutex: three grow-only stream-ordered buffers (hipMallocAsync / hipFreeAsync), event hand-off when the handle's
+// stream changes, skip-scaling cache (hook.cu:70-162,331-374,684-727); hipblasDestroy frees the state first (hook.cu:846-856).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <hipblas/hipblas.h>
+#include <hipblaslt/hipblaslt.h>
 
 #include <algorithm>
 #include <atomic>
@@ -35,6 +51,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -42,44 +59,87 @@
 #include "../../include/gemmul8_c.h"
 #include "../../include/gemmul8_dist.h"
 
+// The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
+// `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
+// then stays 0); the shim, which binds to this project's own libgemmul8.so, requires every entry.
+#define OZ2_ABI(X)                                                                                          \
+    X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
+    X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
+    X(set_nonfinite_mode, __attribute__((weak)))
+#ifndef OZ2_HOOK_SHIM
+#define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
+OZ2_ABI(X)
+#undef X
+#endif
+// the rocBLAS routines the hook calls without defining them (rocblas_status / rocblas_handle as plain int / void*, see the rocBLAS entry
+// points below); declared for decltype only, never referenced
+extern "C" int rocblas_get_stream(void*, hipStream_t*);
+extern "C" int rocblas_get_version_string_size(size_t*);
+extern "C" int rocblas_get_version_string(char*, size_t);
+
+namespace {
+
+// ---- libraries: the real routines and the C ABI
+// an already-mapped library whose path contains `needle`, found in /proc/self/maps and re-opened (never loaded) with the given scope
+void* mapped_library(const char* needle, int scope) {
+    void* r = nullptr;
+    if (FILE* f = std::fopen("/proc/self/maps", "r")) {
+        char line[1024];
+        while (std::fgets(line, sizeof line, f)) {
+            if (!std::strstr(line, needle)) continue;
+            char* path = std::strchr(line, '/');
+            if (!path) continue;
+            path[std::strcspn(path, "\n")] = 0;
+            r = dlopen(path, RTLD_NOW | scope | RTLD_NOLOAD);
+            if (r) break;
+        }
+        std::fclose(f);
+    }
+    return r;
+}
+// the already-mapped copy of the library an interposed name belongs to (each looked up once, on first need)
+void* home_library(const char* name) {
+    if (std::strncmp(name, "hipblasLt", 9) == 0) {
+        static void* const h = mapped_library("libhipblaslt.so", RTLD_LOCAL);
+        return h;
+    }
+    if (std::strstr(name, "rocblas_")) {  // the C entry points and the mangled rocblas_internal_gemm_template names
+        static void* const h = mapped_library("librocblas.so", RTLD_LOCAL);
+        return h;
+    }
+    static void* const h = mapped_library("libhipblas.so", RTLD_LOCAL);  // not libhipblaslt
+    return h;
+}
+// The real routine behind an interposed name (Fn = decltype(&NAME): the hook defines a function of exactly that name and type): the next
+// definition in the global search order, or -- when the host loaded the library privately (Python extension modules are dlopen'ed
+// RTLD_LOCAL) -- the one in the library's mapped copy.
+template <typename Fn> Fn real(const char* name) {
+    void* f = dlsym(RTLD_NEXT, name);
+    if (!f)
+        if (void* lib = home_library(name)) f = dlsym(lib, name);
+    return reinterpret_cast<Fn>(f);
+}
+#define OZ2_REAL(NAME) static const auto real_ = real<decltype(&NAME)>(#NAME)
+// every pass-through runs inside a NativeScope (below)
+#define OZ2_NATIVE(NAME, MISSING, ...) \
+    OZ2_REAL(NAME);                    \
+    NativeScope ns_;                   \
+    return real_ ? real_(__VA_ARGS__) : MISSING
+
+struct Abi {
+#define X(name, attr) decltype(&::gemmul8_##name) name = nullptr;
+    OZ2_ABI(X)
+#undef X
+};
 #ifdef OZ2_HOOK_SHIM
 // Preload shim for hosts that load their HIP runtime late and privately (Python/PyTorch): this library contains no device
 // code (so nothing registers with the HIP runtime when the loader maps it at process start) and binds to libgemmul8.so --
 // which does -- on the first intercepted call: by then the host's libamdhip64 is mapped; it is promoted to the global symbol
-// scope, then libgemmul8.so (found next to this file) is opened and the two C-ABI entry points the hook needs are resolved.
-#include <dlfcn.h>
-#include <string>
-namespace {
-struct Abi {
-    size_t (*work_size)(int, int, size_t, size_t, size_t, unsigned, int, int, size_t*, size_t*) = nullptr;
-    int (*gemm)(void*, int, int, int, int, size_t, size_t, size_t, const void*, const void*, size_t, const void*, size_t, const void*, void*,
-                size_t, unsigned, int, void*, void*, void*, int, int, int, int, double*) = nullptr;
-    decltype(&::gemmul8_work_size_batched) work_size_batched = nullptr;
-    decltype(&::gemmul8_gemm_batched) gemm_batched = nullptr;
-    decltype(&::gemmul8_add_row_bias) add_row_bias = nullptr;
-    decltype(&::gemmul8_comm_rccl_from_env) comm_from_env = nullptr;
-    decltype(&::gemmul8_dist_create) dist_create = nullptr;
-    decltype(&::gemmul8_dist_gemm) dist_gemm = nullptr;
-    decltype(&::gemmul8_dist_allgather_c) dist_allgather_c = nullptr;
-    decltype(&::gemmul8_dist_destroy) dist_destroy = nullptr;
-    decltype(&::gemmul8_set_fp8_bound_mode) set_fp8_bound_mode = nullptr;
-    decltype(&::gemmul8_set_nonfinite_mode) set_nonfinite_mode = nullptr;
-};
+// scope, then libgemmul8.so (found next to this file) is opened and the C-ABI entry points the hook needs are resolved.
 const Abi& abi() {
     static const Abi a = [] {
         Abi r;
-        if (FILE* f = std::fopen("/proc/self/maps", "r")) {  // promote the HIP runtime the process already uses
-            char line[1024];
-            while (std::fgets(line, sizeof line, f)) {
-                if (!std::strstr(line, "libamdhip64")) continue;
-                char* path = std::strchr(line, '/');
-                if (!path) continue;
-                path[std::strcspn(path, "\n")] = 0;
-                (void)dlopen(path, RTLD_NOW | RTLD_GLOBAL | RTLD_NOLOAD);
-                break;
-            }
-            std::fclose(f);
-        }
+        (void)mapped_library("libamdhip64", RTLD_GLOBAL);  // promote the HIP runtime the process already uses
         Dl_info info;
         std::string dir = ".";
         if (dladdr((const void*)&abi, &info) && info.dli_fname) {
@@ -92,50 +152,27 @@ const Abi& abi() {
             std::fprintf(stderr, "[GEMMUL8 HOOK] cannot open %s/libgemmul8.so: %s\n", dir.c_str(), dlerror());
             std::abort();
         }
-        r.work_size = (decltype(r.work_size))dlsym(h, "gemmul8_work_size");
-        r.gemm = (decltype(r.gemm))dlsym(h, "gemmul8_gemm");
-        r.work_size_batched = (decltype(r.work_size_batched))dlsym(h, "gemmul8_work_size_batched");
-        r.gemm_batched = (decltype(r.gemm_batched))dlsym(h, "gemmul8_gemm_batched");
-        r.add_row_bias = (decltype(r.add_row_bias))dlsym(h, "gemmul8_add_row_bias");
-        r.comm_from_env = (decltype(r.comm_from_env))dlsym(h, "gemmul8_comm_rccl_from_env");
-        r.dist_create = (decltype(r.dist_create))dlsym(h, "gemmul8_dist_create");
-        r.dist_gemm = (decltype(r.dist_gemm))dlsym(h, "gemmul8_dist_gemm");
-        r.dist_allgather_c = (decltype(r.dist_allgather_c))dlsym(h, "gemmul8_dist_allgather_c");
-        r.dist_destroy = (decltype(r.dist_destroy))dlsym(h, "gemmul8_dist_destroy");
-        r.set_fp8_bound_mode = (decltype(r.set_fp8_bound_mode))dlsym(h, "gemmul8_set_fp8_bound_mode");
-        r.set_nonfinite_mode = (decltype(r.set_nonfinite_mode))dlsym(h, "gemmul8_set_nonfinite_mode");
-        if (!r.work_size || !r.gemm || !r.work_size_batched || !r.gemm_batched || !r.add_row_bias || !r.comm_from_env || !r.dist_create || !r.dist_gemm || !r.dist_allgather_c || !r.dist_destroy || !r.set_fp8_bound_mode || !r.set_nonfinite_mode) {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] libgemmul8.so lacks the C ABI entry points\n");
-            std::abort();
-        }
+#define X(name, attr)                                                                                                \
+    if (!(r.name = (decltype(r.name))dlsym(h, "gemmul8_" #name))) {                                                  \
+        std::fprintf(stderr, "[GEMMUL8 HOOK] libgemmul8.so lacks the C ABI entry point gemmul8_" #name "\n");        \
+        std::abort();                                                                                                \
+    }
+        OZ2_ABI(X)
+#undef X
         return r;
     }();
     return a;
 }
-}  // namespace
-#define gemmul8_work_size abi().work_size
-#define gemmul8_gemm abi().gemm
-#define gemmul8_work_size_batched abi().work_size_batched
-#define gemmul8_gemm_batched abi().gemm_batched
-#define gemmul8_add_row_bias abi().add_row_bias
-#define gemmul8_comm_rccl_from_env abi().comm_from_env
-#define gemmul8_dist_create abi().dist_create
-#define gemmul8_dist_gemm abi().dist_gemm
-#define gemmul8_dist_allgather_c abi().dist_allgather_c
-#define gemmul8_dist_destroy abi().dist_destroy
-#define gemmul8_set_fp8_bound_mode abi().set_fp8_bound_mode
-namespace {
-int (*nonfinite_setter())(int) { return abi().set_nonfinite_mode; }
-}  // namespace
 #else
-// weak: a build that links this file against a library without the setter (tests/sanitize/mock_gpu.cpp) still loads; the mode then stays 0
-extern "C" __attribute__((weak)) int gemmul8_set_nonfinite_mode(int mode);
-namespace {
-int (*nonfinite_setter())(int) { return &gemmul8_set_nonfinite_mode; }
-}  // namespace
+const Abi& abi() {
+    static const Abi a = {
+#define X(name, attr) &::gemmul8_##name,
+        OZ2_ABI(X)
+#undef X
+    };
+    return a;
+}
 #endif
-
-namespace {
 
 struct Cache {  // what the quantised planes in workA/workB currently hold
     bool valid = false;
@@ -204,18 +241,81 @@ int env_backend(const char* name, int def, bool allow_both) {
     return def;
 }
 
-struct TypeInfo {
+// ---- types, calls and what the environment selects for them
+struct TypeInfo {  // indexed by GEMMUL8_{S,D,C,Z}
     const char* nmod;
     const char* fast;
     unsigned max_moduli;
     bool cplx;
+    size_t elem;  // bytes
+    hipDataType hip_type;
+    hipblasComputeType_t compute;
+    int rocblas_type;  // rocblas_datatype_{f32,f64}_{r,c}
 };
 const TypeInfo kTypes[4] = {
-    {"GEMMUL8_NUM_MOD_S", "GEMMUL8_FASTMODE_S", 13u, false},
-    {"GEMMUL8_NUM_MOD_D", "GEMMUL8_FASTMODE_D", 20u, false},
-    {"GEMMUL8_NUM_MOD_C", "GEMMUL8_FASTMODE_C", 13u, true},
-    {"GEMMUL8_NUM_MOD_Z", "GEMMUL8_FASTMODE_Z", 20u, true},
+    {"GEMMUL8_NUM_MOD_S", "GEMMUL8_FASTMODE_S", 13u, false, 4, HIP_R_32F, HIPBLAS_COMPUTE_32F, 151},
+    {"GEMMUL8_NUM_MOD_D", "GEMMUL8_FASTMODE_D", 20u, false, 8, HIP_R_64F, HIPBLAS_COMPUTE_64F, 152},
+    {"GEMMUL8_NUM_MOD_C", "GEMMUL8_FASTMODE_C", 13u, true, 8, HIP_C_32F, HIPBLAS_COMPUTE_32F, 154},
+    {"GEMMUL8_NUM_MOD_Z", "GEMMUL8_FASTMODE_Z", 20u, true, 16, HIP_C_64F, HIPBLAS_COMPUTE_64F, 155},
 };
+// GEMMUL8_{S,D,C,Z} for a hipDataType (an Lt layout's type included) / a rocblas_datatype code, -1 for every other type
+int dtype_of(int hip_type) {
+    for (int d = 0; d < 4; ++d)
+        if ((int)kTypes[d].hip_type == hip_type) return d;
+    return -1;
+}
+int dtype_of_rocblas(int code) {
+    for (int d = 0; d < 4; ++d)
+        if (kTypes[d].rocblas_type == code) return d;
+    return -1;
+}
+// the *GemmEx forms: same (computeType, A/B/C type) dispatch as hook.cu:961-1030
+int dtype_of(hipDataType aType, hipDataType bType, hipDataType cType, hipblasComputeType_t computeType) {
+    const int d = (aType == bType && bType == cType) ? dtype_of((int)aType) : -1;
+    return d >= 0 && kTypes[d].compute == computeType ? d : -1;
+}
+
+// One GEMM (batch == 1) or one strided batch as the emulator takes it: int dimensions, strides in elements
+struct GemmCall {
+    int dtype;
+    size_t elem;  // bytes
+    hipblasOperation_t ta, tb;
+    int m, n, k;
+    const void *alpha, *A;
+    int lda;
+    long long sa;
+    const void* B;
+    int ldb;
+    long long sb;
+    const void* beta;
+    void* C;
+    int ldc;
+    long long sc;
+    int batch;
+};
+// false = not a call the emulator can be asked about: not an S/D/C/Z type, an empty product or batch, a null matrix, or a dimension an
+// int cannot hold (the ILP64 forms; the reference's CUDA-side hook predates them)
+bool gemm_call(GemmCall* c, int dtype, int ta, int tb, int64_t m, int64_t n, int64_t k, const void* alpha, const void* A, int64_t lda, long long sa,
+               const void* B, int64_t ldb, long long sb, const void* beta, void* C, int64_t ldc, long long sc, int64_t batch = 1) {
+    const int64_t lim = 2147483647;
+    if (dtype < 0 || m <= 0 || n <= 0 || k <= 0 || batch <= 0 || !A || !B || !C) return false;
+    if (m > lim || n > lim || k > lim || lda > lim || ldb > lim || ldc > lim || batch > lim) return false;
+    *c = GemmCall{dtype, kTypes[dtype].elem, (hipblasOperation_t)ta, (hipblasOperation_t)tb, (int)m, (int)n, (int)k, alpha, A, (int)lda, sa, B, (int)ldb, sb,
+                  beta, C, (int)ldc, sc, (int)batch};
+    return true;
+}
+
+struct Selection { unsigned N; bool fast; int backend; bool enA, enB; };
+// what the environment asks for a type, read anew on every call; false = the moduli count does not select emulation
+bool selection_from_env(int dtype, Selection* s) {
+    const TypeInfo& ti = kTypes[dtype];
+    *s = Selection{(unsigned)env_u64(ti.nmod, 0), env_one(ti.fast), env_backend("GEMMUL8_BACKEND", 0, false), env_one("GEMMUL8_SKIP_SCALE_A"),
+                   env_one("GEMMUL8_SKIP_SCALE_B")};
+    return s->N >= 2u && s->N <= ti.max_moduli;
+}
+// the emulator's k range (gemmul8_gemm / gemmul8_gemm_batched return GEMMUL8_E_ARG beyond it)
+constexpr int kMaxK = 1 << 17, kMaxKFp8 = 65536;
+bool k_in_range(const GemmCall& c, const Selection& s) { return c.k <= (s.backend == GEMMUL8_FP8 ? kMaxKFp8 : kMaxK); }
 
 // process-wide workspace floor, computed once (hook.cu:232-281)
 size_t g_maxA = 0, g_maxB = 0, g_maxC = 0;
@@ -225,12 +325,12 @@ void init_max_workspace() {
         // GEMMUL8_FP8_BOUND=reference (this build only): the reference's (k+1)*2^-24 inflation of the FP8 bound GEMM instead of the
         // engine-safe default (include/gemmul8_c.h, gemmul8_set_fp8_bound_mode)
         if (const char* fb = std::getenv("GEMMUL8_FP8_BOUND"))
-            if (!std::strcmp(fb, "reference")) (void)gemmul8_set_fp8_bound_mode(1);
+            if (!std::strcmp(fb, "reference")) (void)abi().set_fp8_bound_mode(1);
         // GEMMUL8_NONFINITE=ieee: BLAS-like NaN / Inf propagation (include/gemmul8_c.h, gemmul8_set_nonfinite_mode); unset or `reference`: mode 0.
         // Not applied to the calls the multi-GPU plans take (GEMMUL8_DIST).
         if (const char* nf = std::getenv("GEMMUL8_NONFINITE"); nf && *nf) {
             if (!std::strcmp(nf, "ieee")) {
-                if (int (*set)(int) = nonfinite_setter()) (void)set(1);
+                if (auto set = abi().set_nonfinite_mode) (void)set(1);
             } else if (std::strcmp(nf, "reference")) {
                 std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=%s not understood (ieee | reference): non-finite mode 0\n", nf);
             }
@@ -243,7 +343,7 @@ void init_max_workspace() {
             if (!(which == be || which == 2)) continue;
             if (mmod < 2 || mmod > 20) continue;
             size_t wa = 0, wb = 0;
-            const size_t w = gemmul8_work_size(cplx, be, mm, mn, mk, mmod, 1, 1, &wa, &wb);
+            const size_t w = abi().work_size(cplx, be, mm, mn, mk, mmod, 1, 1, &wa, &wb);
             g_maxA = std::max(g_maxA, wa);
             g_maxB = std::max(g_maxB, wb);
             g_maxC = std::max(g_maxC, w > wa + wb ? w - wa - wb : 0);
@@ -273,44 +373,8 @@ hipblasStatus_t grow(Buffer& b, size_t need, hipStream_t stream, const char* tag
     return HIPBLAS_STATUS_SUCCESS;
 }
 
-// The real hipBLAS entry point: the next definition in the global search order, or -- when the host loaded hipBLAS privately
-// (Python extension modules are dlopen'ed RTLD_LOCAL) -- the copy of libhipblas that is already mapped into the process.
-void* mapped_library(const char* needle) {
-    void* r = nullptr;
-    if (FILE* f = std::fopen("/proc/self/maps", "r")) {
-        char line[1024];
-        while (std::fgets(line, sizeof line, f)) {
-            if (!std::strstr(line, needle)) continue;
-            char* path = std::strchr(line, '/');
-            if (!path) continue;
-            path[std::strcspn(path, "\n")] = 0;
-            r = dlopen(path, RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-            if (r) break;
-        }
-        std::fclose(f);
-    }
-    return r;
-}
-void* mapped_hipblas() {
-    static void* h = mapped_library("libhipblas.so");  // not libhipblaslt
-    return h;
-}
-void* mapped_hipblaslt() {
-    static void* h = mapped_library("libhipblaslt.so");
-    return h;
-}
-template <typename Fn> Fn real_fn(const char* name) {
-    void* f = dlsym(RTLD_NEXT, name);
-    if (!f)
-        if (void* h = (std::strncmp(name, "hipblasLt", 9) == 0 ? mapped_hipblaslt() : mapped_hipblas())) f = dlsym(h, name);
-    return reinterpret_cast<Fn>(f);
-}
-
 hipStream_t handle_stream(hipblasHandle_t h, hipblasStatus_t* st) {
-    using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipStream_t*);
-    static Fn fn = [] {
-        return real_fn<Fn>("hipblasGetStream");
-    }();
+    static const auto fn = real<decltype(&hipblasGetStream)>("hipblasGetStream");
     hipStream_t s = nullptr;
     *st = fn ? fn(h, &s) : HIPBLAS_STATUS_NOT_INITIALIZED;
     return s;
@@ -331,7 +395,26 @@ hipblasStatus_t order_streams(HandleState& st, hipStream_t cur) {
     return HIPBLAS_STATUS_SUCCESS;
 }
 
-// returns true and sets *status when the call was emulated; false -> caller passes through
+// The handle's state, locked for as long as this object lives, and the stream the call runs on, ordered after the handle's previous one
+// (st != SUCCESS: neither).  explicit_stream: hipblasLtMatmul and the rocBLAS entry points carry / look up their stream themselves; such
+// a handle is no hipblasHandle_t and is marked so that it never reaches hipblasGetStream (release_state).
+struct LockedState {
+    std::shared_ptr<HandleState> sp;
+    std::unique_lock<std::mutex> lk;
+    hipStream_t stream = nullptr;
+    hipblasStatus_t st = HIPBLAS_STATUS_SUCCESS;
+};
+LockedState lock_ordered(hipblasHandle_t handle, const hipStream_t* explicit_stream) {
+    LockedState l;
+    l.sp = state_of(handle);
+    l.lk = std::unique_lock<std::mutex>(l.sp->mtx);
+    if (explicit_stream) l.sp->is_lt = true;
+    init_max_workspace();
+    l.stream = explicit_stream ? *explicit_stream : handle_stream(handle, &l.st);
+    if (l.st == HIPBLAS_STATUS_SUCCESS) l.st = order_streams(*l.sp, l.stream);
+    return l;
+}
+
 // ---- GEMMUL8_DIST = blocks | moduli | fp64sum (not in the reference, which is single-GPU): an SPMD application -- every rank of a
 // torchrun / mpirun job issuing the SAME GEMM calls on replicated operands, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in its
 // environment -- gets each emulated GEMM sharded over the ranks' GPUs by the plans of include/gemmul8_dist.h; the result is
@@ -375,13 +458,11 @@ int dist_kind_from_env() {
 // and the environment (negative GEMMUL8_E_ARG / _NUM_MODULI / _UNSUPPORTED from plan creation, no communicator at all).  A
 // resource failure on one rank (GEMMUL8_E_INTERNAL: allocation, transport) is reported as HIPBLAS_STATUS_INTERNAL_ERROR instead: a
 // rank that silently computed alone would leave its peers waiting in a collective.
-bool try_dist(int kind, int dtype, int backend, hipblasOperation_t ta, hipblasOperation_t tb, int m, int n, int k, const void* alpha, const void* A,
-              int lda, const void* B, int ldb, const void* beta, void* C, int ldc, unsigned N, bool fastmode, hipStream_t stream,
-              hipblasStatus_t* status) {
+bool try_dist(int kind, const GemmCall& c, const Selection& s, hipStream_t stream, hipblasStatus_t* status) {
     std::lock_guard<std::mutex> lk(g_dist.mtx);
     if (g_dist.failed) return false;
     if (!g_dist.comm) {
-        const int rc = gemmul8_comm_rccl_from_env(&g_dist.comm);
+        const int rc = abi().comm_rccl_from_env(&g_dist.comm);
         if (rc != 0 || !g_dist.comm) {
             // decided before any collective has been issued; ncclCommInitRank itself fails on every rank when one is missing
             std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_DIST is set but no RCCL communicator could be created (status %d; RANK/WORLD_SIZE/"
@@ -394,7 +475,7 @@ bool try_dist(int kind, int dtype, int backend, hipblasOperation_t ta, hipblasOp
     // chain behind the previous sharded call (any handle, any stream)
     if (g_dist.have_tail && g_dist.tail_stream != stream && hipStreamWaitEvent(stream, g_dist.tail, 0) != hipSuccess)
         return *status = HIPBLAS_STATUS_INTERNAL_ERROR, true;
-    const DistKey key{kind, dtype, backend, (int)ta, (int)tb, fastmode ? 1 : 0, (size_t)m, (size_t)n, (size_t)k, N};
+    const DistKey key{kind, c.dtype, s.backend, (int)c.ta, (int)c.tb, s.fast ? 1 : 0, (size_t)c.m, (size_t)c.n, (size_t)c.k, s.N};
     gemmul8_dist_plan* plan = nullptr;
     for (size_t i = 0; i < g_dist.plans.size(); ++i)
         if (g_dist.plans[i].first == key) {
@@ -406,11 +487,11 @@ bool try_dist(int kind, int dtype, int backend, hipblasOperation_t ta, hipblasOp
         if (g_dist.plans.size() >= 8) {  // plans own workspaces of the problem's size: keep only a few
             // every earlier sharded call is an ancestor of `tail`: once it has completed no stream still uses the evicted plan
             if (g_dist.have_tail && hipEventSynchronize(g_dist.tail) != hipSuccess) (void)hipDeviceSynchronize();
-            gemmul8_dist_destroy(g_dist.plans.front().second);
+            abi().dist_destroy(g_dist.plans.front().second);
             g_dist.plans.erase(g_dist.plans.begin());
         }
-        const int rc = gemmul8_dist_create(g_dist.comm, nullptr, kind, 0, dtype, backend, (int)ta, (int)tb, (size_t)m, (size_t)n, (size_t)k, N,
-                                           fastmode ? 1 : 0, &plan);
+        const int rc = abi().dist_create(g_dist.comm, nullptr, kind, 0, c.dtype, s.backend, (int)c.ta, (int)c.tb, (size_t)c.m, (size_t)c.n, (size_t)c.k,
+                                         s.N, s.fast ? 1 : 0, &plan);
         if (rc == GEMMUL8_E_INTERNAL || rc > 0 || (rc == 0 && !plan)) {
             std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_DIST: creating the plan failed on this rank (status %d): returning an error (the other "
                                  "ranks are entering the collective)\n", rc);
@@ -419,8 +500,8 @@ bool try_dist(int kind, int dtype, int backend, hipblasOperation_t ta, hipblasOp
         if (rc != 0) return false;  // a property of the arguments (outside the emulator's range): every rank declines alike
         g_dist.plans.emplace_back(key, plan);
     }
-    int rc = gemmul8_dist_gemm(plan, stream, alpha, A, (size_t)lda, B, (size_t)ldb, beta, C, (size_t)ldc);
-    if (rc == 0) rc = gemmul8_dist_allgather_c(plan, stream, C, (size_t)ldc);
+    int rc = abi().dist_gemm(plan, stream, c.alpha, c.A, (size_t)c.lda, c.B, (size_t)c.ldb, c.beta, c.C, (size_t)c.ldc);
+    if (rc == 0) rc = abi().dist_allgather_c(plan, stream, c.C, (size_t)c.ldc);
     if (hipEventRecord(g_dist.tail, stream) == hipSuccess) g_dist.tail_stream = stream, g_dist.have_tail = true;
     else rc = rc ? rc : 1;
     *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR;
@@ -473,11 +554,11 @@ void HookStats::dump() {
     std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu GEMM calls (%.3f TFLOP), native %llu GEMM calls through the hooked entry points (%.3f TFLOP)\n",
                  h.emu_calls.load(), h.emu_mflops.load() * 1e-6, h.nat_calls.load(), h.nat_mflops.load() * 1e-6);
 }
-void count_call(bool emulated, int dtype, double m, double n, double k, double batch = 1.0) {
+void count_call(bool emulated, const GemmCall& c) {
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
     if (!on) return;
     HookStats& h = hook_stats();
-    const unsigned long long mf = (unsigned long long)(2.0 * m * n * k * batch * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
+    const unsigned long long mf = (unsigned long long)(2.0 * c.m * c.n * c.k * c.batch * (c.dtype >= 2 ? 4.0 : 1.0) * 1e-6);
     (emulated ? h.emu_calls : h.nat_calls).fetch_add(1, std::memory_order_relaxed);
     (emulated ? h.emu_mflops : h.nat_mflops).fetch_add(mf, std::memory_order_relaxed);
 }
@@ -487,13 +568,13 @@ struct FloorModel {
     double n[3];  // ms: 1, mn, mnk
 };
 // generated by tools/fit_floor.py from profiles/sweeps/r06_floor_scan_*.csv (the round-6 kernels: accurate mode two launches shorter, short-k epilogue +3-5 %; round 4's fit: r04b_floor_scan_*.csv)
-static const FloorModel kFloor[4][2] = {  // [S, D, C, Z][accurate, fast]
+const FloorModel kFloor[4][2] = {  // [S, D, C, Z][accurate, fast]
     {{{0.05373, 2.353e-09, 3.999e-10, 1.821e-09, 3.555e-10, 6.155e-13}, {0.02155, 4.627e-10, 1.407e-11}}, {{0.04309, 1.051e-09, 4.238e-10, 1.091e-09, 3.574e-10, 5.79e-13}, {0.02155, 4.627e-10, 1.407e-11}}},
     {{{0.04743, 3.922e-09, 4.089e-10, 1.218e-09, 5.024e-10, 5.943e-13}, {0.01043, 8.077e-10, 2.819e-11}}, {{0.03986, 1.88e-09, 4.137e-10, 4.544e-10, 4.8e-10, 5.863e-13}, {0.01043, 8.077e-10, 2.819e-11}}},
     {{{0.06931, 6.912e-09, 1.196e-09, 3.604e-09, 1.806e-09, 1.761e-12}, {0.01406, 2.65e-10, 5.735e-11}}, {{0.05653, 2.963e-09, 1.234e-09, 2.005e-09, 1.787e-09, 1.72e-12}, {0.01406, 2.65e-10, 5.735e-11}}},
     {{{0.07734, 1.242e-08, 1.326e-09, 1.842e-09, 2.131e-09, 1.734e-12}, {0.01304, 2.591e-10, 1.098e-10}}, {{0.06313, 7.525e-09, 1.292e-09, 9.713e-10, 2.174e-09, 1.625e-12}, {0.01304, 2.591e-10, 1.098e-10}}},
 };
-static bool floor_model_declines(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch) {
+bool floor_model_declines(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch) {
     const FloorModel& fm = kFloor[dtype][fast ? 1 : 0];
     const double mk = (m + n) * k, mn = m * n, mnk = mn * k, Nd = (double)N;
     double te = fm.e[0] + batch * ((fm.e[1] + fm.e[2] * Nd) * mk + (fm.e[3] + fm.e[4] * Nd) * mn + fm.e[5] * Nd * mnk);
@@ -525,27 +606,12 @@ bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast,
     return declined;
 }
 
-}  // namespace
-extern "C" GEMMUL8_API int gemmul8_hook_would_emulate(int dtype, int backend, size_t m, size_t n, size_t k, unsigned num_moduli, int fastmode,
-                                                      size_t batch) {
-    if (dtype < 0 || dtype > 3 || (backend != GEMMUL8_INT8 && backend != GEMMUL8_FP8) || batch == 0 || num_moduli < 2 ||
-        num_moduli > kTypes[dtype].max_moduli)
-        return GEMMUL8_E_ARG;
-    if (m == 0 || n == 0 || k == 0) return 0;
-    return below_floor(dtype, (double)m, (double)n, (double)k, num_moduli, fastmode != 0, backend, (double)batch, true) ? 0 : 1;
-}
-namespace {
-// explicit_stream: hipblasLtMatmul carries its stream as an argument (a hipblasLt handle has none)
-bool try_emulate_impl(int dtype, hipblasHandle_t handle, hipblasOperation_t ta, hipblasOperation_t tb, int m, int n, int k, const void* alpha,
-                      const void* A, int lda, const void* B, int ldb, const void* beta, void* C, int ldc, hipblasStatus_t* status,
-                      const hipStream_t* explicit_stream) {
-    const TypeInfo& ti = kTypes[dtype];
-    const unsigned N = (unsigned)env_u64(ti.nmod, 0);
-    if (N < 2u || N > ti.max_moduli) return false;
-    const bool fastmode = env_one(ti.fast);
-    const bool enA = env_one("GEMMUL8_SKIP_SCALE_A"), enB = env_one("GEMMUL8_SKIP_SCALE_B");
-    const int backend = env_backend("GEMMUL8_BACKEND", 0, false);
-    if (backend == GEMMUL8_FP8) {
+// "Does the environment select emulation for this call?": a moduli count in the type's range, and the call not below the floor.  The k
+// range is a separate question (k_in_range): the single-call path leaves it to gemmul8_gemm, whose decline is logged once; the batched
+// and hipblasLt paths ask first, because they commit to a path (or touch D) before the emulator is called.
+bool selected(const GemmCall& c, Selection* s, bool fp8_notice = false) {
+    if (!selection_from_env(c.dtype, s)) return false;
+    if (fp8_notice && s->backend == GEMMUL8_FP8) {
         // the FP8 backend exists for parity with the reference; on this chip the INT8 backend dominates it: three GEMMs per modulus (on FP6 codes
         // of the backend's integer pieces, 1.5x the INT8 kernel's rate since round 5) against one INT8 GEMM (profiles/sweeps/r05_types_backends.csv:
         // SGEMM 8192^3 193 vs 302 TFLOPS, native 153; DGEMM 101 vs 160, native 71).  Say so once.
@@ -555,23 +621,29 @@ bool try_emulate_impl(int dtype, hipblasHandle_t handle, hipblasOperation_t ta, 
                                  "accuracy for S/D/C/Z; continuing with FP8 as requested\n");
         });
     }
-    if (below_floor(dtype, m, n, k, N, fastmode, backend)) return false;
+    return !below_floor(c.dtype, c.m, c.n, c.k, s->N, s->fast, s->backend, (double)c.batch);
+}
 
-    auto sp = state_of(handle);
-    std::lock_guard<std::mutex> lk(sp->mtx);
-    if (explicit_stream) sp->is_lt = true;
-    init_max_workspace();
-    hipblasStatus_t st = HIPBLAS_STATUS_SUCCESS;
-    hipStream_t stream = explicit_stream ? *explicit_stream : handle_stream(handle, &st);
-    if (st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
-    if ((st = order_streams(*sp, stream)) != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
+// one GEMM (c.batch == 1) on the handle's stream and buffers; returns true and sets *status when the call was served here (emulated, or
+// failed), false -> the caller passes it through
+bool try_emulate_impl(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* status, const hipStream_t* explicit_stream) {
+    Selection s;
+    if (!selected(c, &s, true)) return false;
+    const int dtype = c.dtype, backend = s.backend;
+    const unsigned N = s.N;
+    const bool fastmode = s.fast, enA = s.enA, enB = s.enB;
+
+    LockedState l = lock_ordered(handle, explicit_stream);
+    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
+    HandleState* const sp = l.sp.get();
+    hipStream_t stream = l.stream;
+    hipblasStatus_t st;
 
     const int dist_kind = dist_kind_from_env();
-    if (dist_kind >= 0 && try_dist(dist_kind, dtype, backend, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, N, fastmode, stream, status))
-        return true;
+    if (dist_kind >= 0 && try_dist(dist_kind, c, s, stream, status)) return true;
 
     size_t needA = 0, needB = 0;
-    const size_t tot = gemmul8_work_size(ti.cplx, backend, (size_t)m, (size_t)n, (size_t)k, N, enA, enB, &needA, &needB);
+    const size_t tot = abi().work_size(kTypes[dtype].cplx, backend, (size_t)c.m, (size_t)c.n, (size_t)c.k, N, enA, enB, &needA, &needB);
     if (tot < needA + needB) return *status = HIPBLAS_STATUS_INVALID_VALUE, true;
     size_t reqA = needA, reqB = needB, reqC = tot - needA - needB;
     if (enA || enB) {  // keep buffers (hence cached planes) stable across differently sized calls
@@ -583,17 +655,16 @@ bool try_emulate_impl(int dtype, hipblasHandle_t handle, hipblasOperation_t ta, 
     if ((st = grow(sp->wB, reqB, stream, "workB")) != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
     if ((st = grow(sp->wC, reqC, stream, "workC")) != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
 
-    const Cache& c = sp->last;
+    const Cache& o = sp->last;
     bool skipA = false, skipB = false;
-    if (c.valid && c.num_moduli == N && c.k == (size_t)k && c.dtype == dtype && c.fastmode == fastmode && c.backend == backend &&
-        c.enA == enA && c.enB == enB) {
-        skipA = enA && c.workA == sp->wA.ptr && c.A == A && c.m == (size_t)m && c.lda == (size_t)lda && c.op_A == (int)ta;
-        skipB = enB && c.workB == sp->wB.ptr && c.B == B && c.n == (size_t)n && c.ldb == (size_t)ldb && c.op_B == (int)tb;
+    if (o.valid && o.num_moduli == N && o.k == (size_t)c.k && o.dtype == dtype && o.fastmode == fastmode && o.backend == backend && o.enA == enA &&
+        o.enB == enB) {
+        skipA = enA && o.workA == sp->wA.ptr && o.A == c.A && o.m == (size_t)c.m && o.lda == (size_t)c.lda && o.op_A == (int)c.ta;
+        skipB = enB && o.workB == sp->wB.ptr && o.B == c.B && o.n == (size_t)c.n && o.ldb == (size_t)c.ldb && o.op_B == (int)c.tb;
     }
     sp->last.valid = false;  // the call below overwrites the planes; the cache is re-validated only if it succeeds
-    const int rc = gemmul8_gemm(stream, dtype, backend, (int)ta, (int)tb, (size_t)m, (size_t)n, (size_t)k, alpha, A, (size_t)lda, B,
-                                (size_t)ldb, beta, C, (size_t)ldc, N, fastmode, sp->wC.ptr, sp->wA.ptr, sp->wB.ptr, enA, enB, skipA, skipB,
-                                nullptr);
+    const int rc = abi().gemm(stream, dtype, backend, (int)c.ta, (int)c.tb, (size_t)c.m, (size_t)c.n, (size_t)c.k, c.alpha, c.A, (size_t)c.lda, c.B,
+                              (size_t)c.ldb, c.beta, c.C, (size_t)c.ldc, N, fastmode, sp->wC.ptr, sp->wA.ptr, sp->wB.ptr, enA, enB, skipA, skipB, nullptr);
     if (rc < 0) {
         // a GEMMUL8_E_* status means "this call is outside what the emulator accepts" (k > 2^17, FP8 with k > 65536, a
         // combination that is not built, ...): nothing has been written to C yet, so the application's call is still valid
@@ -601,7 +672,7 @@ bool try_emulate_impl(int dtype, hipblasHandle_t handle, hipblasOperation_t ta, 
         static std::once_flag warned;
         std::call_once(warned, [&] {
             std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a call (status %d; type %d, backend %d, m=%d n=%d k=%d): using the native routine for such calls\n",
-                         rc, dtype, backend, m, n, k);
+                         rc, dtype, backend, c.m, c.n, c.k);
         });
         return false;
     }
@@ -610,20 +681,18 @@ bool try_emulate_impl(int dtype, hipblasHandle_t handle, hipblasOperation_t ta, 
     u.valid = true;
     u.enA = enA, u.enB = enB;
     u.num_moduli = N;
-    u.op_A = (int)ta, u.op_B = (int)tb;
-    u.m = m, u.n = n, u.k = k, u.lda = lda, u.ldb = ldb;
-    u.A = A, u.B = B;
+    u.op_A = (int)c.ta, u.op_B = (int)c.tb;
+    u.m = c.m, u.n = c.n, u.k = c.k, u.lda = c.lda, u.ldb = c.ldb;
+    u.A = c.A, u.B = c.B;
     u.workA = sp->wA.ptr, u.workB = sp->wB.ptr;
     u.dtype = dtype, u.backend = backend, u.fastmode = fastmode;
     return *status = HIPBLAS_STATUS_SUCCESS, true;
 }
 // counted front end (GEMMUL8_HOOK_STATS): true = the call was served here (emulated, or failed with *status set); false = native routine
-bool try_emulate(int dtype, hipblasHandle_t handle, hipblasOperation_t ta, hipblasOperation_t tb, int m, int n, int k, const void* alpha,
-                 const void* A, int lda, const void* B, int ldb, const void* beta, void* C, int ldc, hipblasStatus_t* status,
-                 const hipStream_t* explicit_stream = nullptr) {
+bool try_emulate(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* status, const hipStream_t* explicit_stream = nullptr) {
     if (tl_native_depth > 0) return false;  // inside a native pass-through of an outer hooked entry: the same call, already declined and counted
-    const bool served = try_emulate_impl(dtype, handle, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, status, explicit_stream);
-    count_call(served, dtype, m, n, k);
+    const bool served = try_emulate_impl(handle, c, status, explicit_stream);
+    count_call(served, c);
     return served;
 }
 
@@ -669,146 +738,6 @@ void release_state(hipblasHandle_t handle, bool lt = false) {
     if (sp->fork) (void)hipEventDestroy(sp->fork), sp->fork = nullptr;
 }
 
-#define OZ2_EARLY_OUT()                                           \
-    if (m <= 0 || n <= 0 || k <= 0) return HIPBLAS_STATUS_SUCCESS; \
-    if (!A || !B || !C) return HIPBLAS_STATUS_INVALID_VALUE;
-
-}  // namespace
-
-#pragma GCC visibility push(default)
-extern "C" {
-
-hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
-    release_state(handle);
-    using Fn = hipblasStatus_t (*)(hipblasHandle_t);
-    static Fn real = real_fn<Fn>("hipblasDestroy");
-    NativeScope ns_; return real ? real(handle) : HIPBLAS_STATUS_NOT_INITIALIZED;
-}
-
-#define OZ2_GEMM_HOOK(NAME, T, CODE)                                                                                                   \
-    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int m, int n, int k,             \
-                         const T* alpha, const T* A, int lda, const T* B, int ldb, const T* beta, T* C, int ldc) {                      \
-        OZ2_EARLY_OUT()                                                                                                                 \
-        hipblasStatus_t st;                                                                                                             \
-        if (try_emulate(CODE, handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;                    \
-        using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const T*, const T*, int, \
-                                       const T*, int, const T*, T*, int);                                                               \
-        static Fn real = real_fn<Fn>(#NAME);                                                                                            \
-        NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc) : HIPBLAS_STATUS_NOT_INITIALIZED;      \
-    }
-OZ2_GEMM_HOOK(hipblasSgemm, float, GEMMUL8_S)
-OZ2_GEMM_HOOK(hipblasDgemm, double, GEMMUL8_D)
-OZ2_GEMM_HOOK(hipblasCgemm, hipComplex, GEMMUL8_C)
-OZ2_GEMM_HOOK(hipblasZgemm, hipDoubleComplex, GEMMUL8_Z)
-#undef OZ2_GEMM_HOOK
-
-hipblasStatus_t hipblasGemmEx(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int m, int n, int k,
-                              const void* alpha, const void* A, hipDataType aType, int lda, const void* B, hipDataType bType, int ldb,
-                              const void* beta, void* C, hipDataType cType, int ldc, hipblasComputeType_t computeType,
-                              hipblasGemmAlgo_t algo) {
-    OZ2_EARLY_OUT()
-    int dtype = -1;  // same (computeType, A/B/C type) dispatch as hook.cu:961-1030
-    const bool same = (aType == bType && bType == cType);
-    if (same && computeType == HIPBLAS_COMPUTE_32F && aType == HIP_R_32F) dtype = GEMMUL8_S;
-    else if (same && computeType == HIPBLAS_COMPUTE_64F && aType == HIP_R_64F) dtype = GEMMUL8_D;
-    else if (same && computeType == HIPBLAS_COMPUTE_32F && aType == HIP_C_32F) dtype = GEMMUL8_C;
-    else if (same && computeType == HIPBLAS_COMPUTE_64F && aType == HIP_C_64F) dtype = GEMMUL8_Z;
-    hipblasStatus_t st;
-    if (dtype >= 0 && try_emulate(dtype, handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;
-    using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const void*, const void*,
-                                   hipDataType, int, const void*, hipDataType, int, const void*, void*, hipDataType, int,
-                                   hipblasComputeType_t, hipblasGemmAlgo_t);
-    static Fn real = real_fn<Fn>("hipblasGemmEx");
-    NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, aType, lda, B, bType, ldb, beta, C, cType, ldc, computeType, algo)
-                : HIPBLAS_STATUS_NOT_INITIALIZED;
-}
-
-// ROCm 7 also exports ILP64 twins (`_64`, int64_t dimensions) and hipblasGemmExWithFlags of the entry points above; the
-// reference's CUDA-side hook predates them.  Same emulation when every dimension fits an int, the native routine otherwise.
-static inline bool fits_int(int64_t a, int64_t b, int64_t c, int64_t d, int64_t e, int64_t f) {
-    const int64_t lim = 2147483647;
-    return a <= lim && b <= lim && c <= lim && d <= lim && e <= lim && f <= lim;
-}
-#define OZ2_GEMM_HOOK_64(NAME, T, CODE)                                                                                                  \
-    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int64_t m, int64_t n, int64_t k,   \
-                         const T* alpha, const T* A, int64_t lda, const T* B, int64_t ldb, const T* beta, T* C, int64_t ldc) {            \
-        OZ2_EARLY_OUT()                                                                                                                   \
-        hipblasStatus_t st;                                                                                                               \
-        if (fits_int(m, n, k, lda, ldb, ldc) &&                                                                                           \
-            try_emulate(CODE, handle, transA, transB, (int)m, (int)n, (int)k, alpha, A, (int)lda, B, (int)ldb, beta, C, (int)ldc, &st))   \
-            return st;                                                                                                                    \
-        using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int64_t, int64_t, int64_t, const T*,      \
-                                       const T*, int64_t, const T*, int64_t, const T*, T*, int64_t);                                      \
-        static Fn real = real_fn<Fn>(#NAME);                                                                                              \
-        NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc) : HIPBLAS_STATUS_NOT_INITIALIZED;        \
-    }
-OZ2_GEMM_HOOK_64(hipblasSgemm_64, float, GEMMUL8_S)
-OZ2_GEMM_HOOK_64(hipblasDgemm_64, double, GEMMUL8_D)
-OZ2_GEMM_HOOK_64(hipblasCgemm_64, hipComplex, GEMMUL8_C)
-OZ2_GEMM_HOOK_64(hipblasZgemm_64, hipDoubleComplex, GEMMUL8_Z)
-#undef OZ2_GEMM_HOOK_64
-
-static int gemm_ex_dtype(hipDataType aType, hipDataType bType, hipDataType cType, hipblasComputeType_t computeType) {
-    const bool same = (aType == bType && bType == cType);  // same (computeType, A/B/C type) dispatch as hook.cu:961-1030
-    if (same && computeType == HIPBLAS_COMPUTE_32F && aType == HIP_R_32F) return GEMMUL8_S;
-    if (same && computeType == HIPBLAS_COMPUTE_64F && aType == HIP_R_64F) return GEMMUL8_D;
-    if (same && computeType == HIPBLAS_COMPUTE_32F && aType == HIP_C_32F) return GEMMUL8_C;
-    if (same && computeType == HIPBLAS_COMPUTE_64F && aType == HIP_C_64F) return GEMMUL8_Z;
-    return -1;
-}
-
-hipblasStatus_t hipblasGemmExWithFlags(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int m, int n, int k,
-                                       const void* alpha, const void* A, hipDataType aType, int lda, const void* B, hipDataType bType, int ldb,
-                                       const void* beta, void* C, hipDataType cType, int ldc, hipblasComputeType_t computeType,
-                                       hipblasGemmAlgo_t algo, hipblasGemmFlags_t flags) {
-    OZ2_EARLY_OUT()
-    const int dtype = gemm_ex_dtype(aType, bType, cType, computeType);
-    hipblasStatus_t st;
-    if (dtype >= 0 && try_emulate(dtype, handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;
-    using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const void*, const void*,
-                                   hipDataType, int, const void*, hipDataType, int, const void*, void*, hipDataType, int,
-                                   hipblasComputeType_t, hipblasGemmAlgo_t, hipblasGemmFlags_t);
-    static Fn real = real_fn<Fn>("hipblasGemmExWithFlags");
-    NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, aType, lda, B, bType, ldb, beta, C, cType, ldc, computeType, algo, flags)
-                : HIPBLAS_STATUS_NOT_INITIALIZED;
-}
-
-hipblasStatus_t hipblasGemmEx_64(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int64_t m, int64_t n, int64_t k,
-                                 const void* alpha, const void* A, hipDataType aType, int64_t lda, const void* B, hipDataType bType,
-                                 int64_t ldb, const void* beta, void* C, hipDataType cType, int64_t ldc, hipblasComputeType_t computeType,
-                                 hipblasGemmAlgo_t algo) {
-    OZ2_EARLY_OUT()
-    const int dtype = gemm_ex_dtype(aType, bType, cType, computeType);
-    hipblasStatus_t st;
-    if (dtype >= 0 && fits_int(m, n, k, lda, ldb, ldc) &&
-        try_emulate(dtype, handle, transA, transB, (int)m, (int)n, (int)k, alpha, A, (int)lda, B, (int)ldb, beta, C, (int)ldc, &st))
-        return st;
-    using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int64_t, int64_t, int64_t, const void*,
-                                   const void*, hipDataType, int64_t, const void*, hipDataType, int64_t, const void*, void*, hipDataType,
-                                   int64_t, hipblasComputeType_t, hipblasGemmAlgo_t);
-    static Fn real = real_fn<Fn>("hipblasGemmEx_64");
-    NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, aType, lda, B, bType, ldb, beta, C, cType, ldc, computeType, algo)
-                : HIPBLAS_STATUS_NOT_INITIALIZED;
-}
-
-hipblasStatus_t hipblasGemmExWithFlags_64(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int64_t m, int64_t n,
-                                          int64_t k, const void* alpha, const void* A, hipDataType aType, int64_t lda, const void* B,
-                                          hipDataType bType, int64_t ldb, const void* beta, void* C, hipDataType cType, int64_t ldc,
-                                          hipblasComputeType_t computeType, hipblasGemmAlgo_t algo, hipblasGemmFlags_t flags) {
-    OZ2_EARLY_OUT()
-    const int dtype = gemm_ex_dtype(aType, bType, cType, computeType);
-    hipblasStatus_t st;
-    if (dtype >= 0 && fits_int(m, n, k, lda, ldb, ldc) &&
-        try_emulate(dtype, handle, transA, transB, (int)m, (int)n, (int)k, alpha, A, (int)lda, B, (int)ldb, beta, C, (int)ldc, &st))
-        return st;
-    using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int64_t, int64_t, int64_t, const void*,
-                                   const void*, hipDataType, int64_t, const void*, hipDataType, int64_t, const void*, void*, hipDataType,
-                                   int64_t, hipblasComputeType_t, hipblasGemmAlgo_t, hipblasGemmFlags_t);
-    static Fn real = real_fn<Fn>("hipblasGemmExWithFlags_64");
-    NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, aType, lda, B, bType, ldb, beta, C, cType, ldc, computeType, algo, flags)
-                : HIPBLAS_STATUS_NOT_INITIALIZED;
-}
-
 // Strided-batched entry points (not hooked by the reference; PyTorch's bmm uses them).  alpha/beta are shared by the batch; element
 // strides are in units of the matrix type.  The items of a batch are independent, and below ~2048^3 one emulated GEMM is ten
 // latency-bound launches that leave most of the chip idle.  Default: one set of launches for the whole batch (below).  Otherwise
@@ -816,32 +745,24 @@ hipblasStatus_t hipblasGemmExWithFlags_64(hipblasHandle_t handle, hipblasOperati
 // serial loop on the handle's stream): lane 0 is the handle's stream with the handle's buffers, every other lane has its own
 // non-blocking stream and workspace; the lanes fork from the handle's stream with an event and join it again before the call
 // returns, so the call stays stream-ordered for the application (and capturable in a HIP graph after one warm-up call).
-static bool emulate_batch(int dtype, size_t elem, hipblasHandle_t handle, hipblasOperation_t ta, hipblasOperation_t tb, int m, int n, int k,
-                          const void* alpha, const void* A, int lda, long long sa, const void* B, int ldb, long long sb, const void* beta,
-                          void* C, int ldc, long long sc, int batch, hipblasStatus_t* status, const hipStream_t* explicit_stream = nullptr) {
+bool emulate_batch(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* status, const hipStream_t* explicit_stream = nullptr) {
     *status = HIPBLAS_STATUS_SUCCESS;
     if (tl_native_depth > 0) return false;  // see try_emulate
-    // First choice (INT8 backend, GEMMUL8_BATCH_FUSED != 0): the whole batch as ONE set of launches (gemmul8_gemm_batched: the items in
+    const int dtype = c.dtype, batch = c.batch;
+    const long long elem = (long long)c.elem;
+    Selection s;
+    // First choice (GEMMUL8_BATCH_FUSED != 0): the whole batch as ONE set of launches (gemmul8_gemm_batched: the items in
     // gridDim.z of every kernel) -- a batch of small matrices then fills the chip and costs ten launches, not ten per item.
     if (batch > 1 && env_u64("GEMMUL8_BATCH_FUSED", 1) != 0 && dist_kind_from_env() < 0) {
-        const TypeInfo& ti = kTypes[dtype];
-        const unsigned N = (unsigned)env_u64(ti.nmod, 0);
-        if (N < 2u || N > ti.max_moduli) return false;
-        const int backend = env_backend("GEMMUL8_BACKEND", 0, false);
-        if (below_floor(dtype, m, n, k, N, env_one(ti.fast), backend, (double)batch)) return false;
-        if (k <= (backend == GEMMUL8_FP8 ? 65536 : (1 << 17))) {
-            const bool fastmode = env_one(ti.fast);
-            auto sp = state_of(handle);
-            std::lock_guard<std::mutex> lk(sp->mtx);
-            if (explicit_stream) sp->is_lt = true;
-            init_max_workspace();
-            hipblasStatus_t st = HIPBLAS_STATUS_SUCCESS;
-            hipStream_t stream = explicit_stream ? *explicit_stream : handle_stream(handle, &st);
-            if (st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
-            if ((st = order_streams(*sp, stream)) != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
+        if (!selected(c, &s)) return false;
+        if (k_in_range(c, s)) {
+            LockedState l = lock_ordered(handle, explicit_stream);
+            if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
+            HandleState* const sp = l.sp.get();
+            hipStream_t stream = l.stream;
             // the items' workspaces are consecutive: bound the buffer (GEMMUL8_BATCH_WORKSPACE_MB, default 4096) and run the batch in
             // chunks of as many items as fit; if even that cannot be allocated the per-item path below takes over
-            const size_t item = gemmul8_work_size_batched(ti.cplx, backend, (size_t)m, (size_t)n, (size_t)k, N, 1) - 256;
+            const size_t item = abi().work_size_batched(kTypes[dtype].cplx, s.backend, (size_t)c.m, (size_t)c.n, (size_t)c.k, s.N, 1) - 256;
             const size_t budget = (size_t)env_u64("GEMMUL8_BATCH_WORKSPACE_MB", 4096) << 20;
             const size_t per_chunk = std::max<size_t>(1, std::min<size_t>((size_t)batch, item ? budget / item : (size_t)batch));
             if (grow(sp->wC, item * per_chunk + 256, stream, "workC (batched)") == HIPBLAS_STATUS_SUCCESS) {
@@ -849,13 +770,13 @@ static bool emulate_batch(int dtype, size_t elem, hipblasHandle_t handle, hipbla
                 int rc = 0;
                 for (size_t b0 = 0; b0 < (size_t)batch && rc == 0; b0 += per_chunk) {
                     const size_t nb = std::min(per_chunk, (size_t)batch - b0);
-                    rc = gemmul8_gemm_batched(stream, dtype, backend, (int)ta, (int)tb, (size_t)m, (size_t)n, (size_t)k, alpha,
-                                              (const char*)A + (long long)b0 * sa * (long long)elem, (size_t)lda, sa,
-                                              (const char*)B + (long long)b0 * sb * (long long)elem, (size_t)ldb, sb, beta,
-                                              (char*)C + (long long)b0 * sc * (long long)elem, (size_t)ldc, sc, nb, N, fastmode, sp->wC.ptr);
+                    rc = abi().gemm_batched(stream, dtype, s.backend, (int)c.ta, (int)c.tb, (size_t)c.m, (size_t)c.n, (size_t)c.k, c.alpha,
+                                            (const char*)c.A + (long long)b0 * c.sa * elem, (size_t)c.lda, c.sa,
+                                            (const char*)c.B + (long long)b0 * c.sb * elem, (size_t)c.ldb, c.sb, c.beta,
+                                            (char*)c.C + (long long)b0 * c.sc * elem, (size_t)c.ldc, c.sc, nb, s.N, s.fast, sp->wC.ptr);
                     if (rc < 0 && b0 > 0) rc = 1;  // declined after earlier chunks were written: cannot hand the call to another path
                 }
-                if (rc == 0) return count_call(true, dtype, m, n, k, (double)batch), true;
+                if (rc == 0) return count_call(true, c), true;
                 if (rc > 0) return *status = HIPBLAS_STATUS_INTERNAL_ERROR, true;
                 // negative on the first chunk: declined (nothing written) -- fall through to the per-item path
             } else {
@@ -863,22 +784,19 @@ static bool emulate_batch(int dtype, size_t elem, hipblasHandle_t handle, hipbla
             }
         }
     }
-    auto item = [&](int b, const void** a, const void** bb, void** c) {
-        *a = (const char*)A + (size_t)b * sa * elem, *bb = (const char*)B + (size_t)b * sb * elem, *c = (char*)C + (size_t)b * sc * elem;
+    auto item = [&](int b) {
+        GemmCall it = c;
+        it.A = (const char*)c.A + (size_t)b * c.sa * c.elem, it.B = (const char*)c.B + (size_t)b * c.sb * c.elem, it.C = (char*)c.C + (size_t)b * c.sc * c.elem;
+        it.batch = 1;
+        return it;
     };
-    const void *Ai, *Bi;
-    void* Ci;
     hipblasStatus_t st;
     // item 0 on the handle's stream decides whether the environment selects emulation for this call at all
-    item(0, &Ai, &Bi, &Ci);
-    if (!try_emulate(dtype, handle, ta, tb, m, n, k, alpha, Ai, lda, Bi, ldb, beta, Ci, ldc, &st, explicit_stream)) return false;
+    if (!try_emulate(handle, item(0), &st, explicit_stream)) return false;
     if (st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
     int lanes = (int)env_u64("GEMMUL8_BATCH_STREAMS", 4);
     lanes = std::max(1, std::min({lanes, kMaxBatchLanes, batch}));
-    const TypeInfo& ti = kTypes[dtype];
-    const unsigned N = (unsigned)env_u64(ti.nmod, 0);
-    const bool fastmode = env_one(ti.fast);
-    const int backend = env_backend("GEMMUL8_BACKEND", 0, false);
+    (void)selection_from_env(dtype, &s);  // item 0 was served with it
     if (lanes > 1 && dist_kind_from_env() >= 0) lanes = 1;  // the sharded path keeps its collectives on one stream
     auto sp = state_of(handle);
     hipStream_t main_stream = nullptr;
@@ -886,7 +804,7 @@ static bool emulate_batch(int dtype, size_t elem, hipblasHandle_t handle, hipbla
         std::lock_guard<std::mutex> lk(sp->mtx);
         main_stream = sp->last_stream;  // set by item 0
         bool ok = sp->fork || hipEventCreateWithFlags(&sp->fork, hipEventDisableTiming) == hipSuccess;
-        const size_t need = gemmul8_work_size(ti.cplx, backend, (size_t)m, (size_t)n, (size_t)k, N, 0, 0, nullptr, nullptr);
+        const size_t need = abi().work_size(kTypes[dtype].cplx, s.backend, (size_t)c.m, (size_t)c.n, (size_t)c.k, s.N, 0, 0, nullptr, nullptr);
         ok = ok && hipEventRecord(sp->fork, main_stream) == hipSuccess;
         for (int l = 1; l < lanes && ok; ++l) {
             BatchLane& ln = sp->lanes[l];
@@ -898,10 +816,10 @@ static bool emulate_batch(int dtype, size_t elem, hipblasHandle_t handle, hipbla
         if (!ok) lanes = 1;  // fall back to the serial loop
     }
     for (int b = 1; b < batch; ++b) {
-        item(b, &Ai, &Bi, &Ci);
+        const GemmCall it = item(b);
         const int l = b % lanes;
         if (l == 0) {
-            const bool done = try_emulate(dtype, handle, ta, tb, m, n, k, alpha, Ai, lda, Bi, ldb, beta, Ci, ldc, &st, explicit_stream);
+            const bool done = try_emulate(handle, it, &st, explicit_stream);
             if (!done || st != HIPBLAS_STATUS_SUCCESS) {  // stop issuing items; the forked lanes are still joined below
                 *status = done ? st : HIPBLAS_STATUS_INTERNAL_ERROR;
                 break;
@@ -909,8 +827,8 @@ static bool emulate_batch(int dtype, size_t elem, hipblasHandle_t handle, hipbla
         } else {
             std::lock_guard<std::mutex> lk(sp->mtx);
             BatchLane& ln = sp->lanes[l];
-            const int rc = gemmul8_gemm(ln.stream, dtype, backend, (int)ta, (int)tb, (size_t)m, (size_t)n, (size_t)k, alpha, Ai, (size_t)lda, Bi,
-                                        (size_t)ldb, beta, Ci, (size_t)ldc, N, fastmode, ln.w.ptr, nullptr, nullptr, 0, 0, 0, 0, nullptr);
+            const int rc = abi().gemm(ln.stream, dtype, s.backend, (int)c.ta, (int)c.tb, (size_t)c.m, (size_t)c.n, (size_t)c.k, c.alpha, it.A, (size_t)c.lda, it.B,
+                                      (size_t)c.ldb, c.beta, it.C, (size_t)c.ldc, s.N, s.fast, ln.w.ptr, nullptr, nullptr, 0, 0, 0, 0, nullptr);
             if (rc != 0) *status = HIPBLAS_STATUS_INTERNAL_ERROR;  // item 0 ran with the same shape and switches: should not happen
         }
     }
@@ -925,76 +843,14 @@ static bool emulate_batch(int dtype, size_t elem, hipblasHandle_t handle, hipbla
     return true;
 }
 
-#define OZ2_SB_HOOK(NAME, T, CODE)                                                                                                       \
-    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int m, int n, int k,               \
-                         const T* alpha, const T* A, int lda, long long strideA, const T* B, int ldb, long long strideB, const T* beta,  \
-                         T* C, int ldc, long long strideC, int batchCount) {                                                             \
-        hipblasStatus_t st;                                                                                                               \
-        if (m > 0 && n > 0 && k > 0 && batchCount > 0 && A && B && C && alpha && beta &&                                                  \
-            emulate_batch(CODE, sizeof(T), handle, transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc,        \
-                          strideC, batchCount, &st))                                                                                      \
-            return st;                                                                                                                    \
-        using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const T*, const T*, int,   \
-                                       long long, const T*, int, long long, const T*, T*, int, long long, int);                          \
-        static Fn real = real_fn<Fn>(#NAME);                                                                                              \
-        NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batchCount)   \
-                    : HIPBLAS_STATUS_NOT_INITIALIZED;                                                                                     \
-    }
-OZ2_SB_HOOK(hipblasSgemmStridedBatched, float, GEMMUL8_S)
-OZ2_SB_HOOK(hipblasDgemmStridedBatched, double, GEMMUL8_D)
-OZ2_SB_HOOK(hipblasCgemmStridedBatched, hipComplex, GEMMUL8_C)
-OZ2_SB_HOOK(hipblasZgemmStridedBatched, hipDoubleComplex, GEMMUL8_Z)
-#undef OZ2_SB_HOOK
-
-hipblasStatus_t hipblasGemmStridedBatchedEx(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int m, int n, int k,
-                                            const void* alpha, const void* A, hipDataType aType, int lda, hipblasStride strideA, const void* B,
-                                            hipDataType bType, int ldb, hipblasStride strideB, const void* beta, void* C, hipDataType cType,
-                                            int ldc, hipblasStride strideC, int batchCount, hipblasComputeType_t computeType,
-                                            hipblasGemmAlgo_t algo) {
-    int dtype = -1;
-    size_t elem = 0;
-    const bool same = (aType == bType && bType == cType);
-    if (same && computeType == HIPBLAS_COMPUTE_32F && aType == HIP_R_32F) dtype = GEMMUL8_S, elem = 4;
-    else if (same && computeType == HIPBLAS_COMPUTE_64F && aType == HIP_R_64F) dtype = GEMMUL8_D, elem = 8;
-    else if (same && computeType == HIPBLAS_COMPUTE_32F && aType == HIP_C_32F) dtype = GEMMUL8_C, elem = 8;
-    else if (same && computeType == HIPBLAS_COMPUTE_64F && aType == HIP_C_64F) dtype = GEMMUL8_Z, elem = 16;
-    hipblasStatus_t st;
-    if (dtype >= 0 && m > 0 && n > 0 && k > 0 && batchCount > 0 && A && B && C && alpha && beta &&
-        emulate_batch(dtype, elem, handle, transA, transB, m, n, k, alpha, A, lda, (long long)strideA, B, ldb, (long long)strideB, beta, C, ldc,
-                      (long long)strideC, batchCount, &st))
-        return st;
-    using Fn = hipblasStatus_t (*)(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const void*, const void*,
-                                   hipDataType, int, hipblasStride, const void*, hipDataType, int, hipblasStride, const void*, void*,
-                                   hipDataType, int, hipblasStride, int, hipblasComputeType_t, hipblasGemmAlgo_t);
-    static Fn real = real_fn<Fn>("hipblasGemmStridedBatchedEx");
-    NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, aType, lda, strideA, B, bType, ldb, strideB, beta, C, cType, ldc, strideC,
-                       batchCount, computeType, algo)
-                : HIPBLAS_STATUS_NOT_INITIALIZED;
-}
-
 
 // ---- rocBLAS entry points, opt-in with GEMMUL8_HOOK_ROCBLAS=1 (no counterpart in the reference: src/hook.cu:846-1055 hooks the cuBLAS / hipBLAS
 // names only).  For applications that call rocBLAS directly.  The handle of a hipBLAS call IS the rocBLAS handle, so a call the hipBLAS hooks
-// above declined arrives here again through the real hipBLAS and is declined again by the same rules.  rocSOLVER / hipSOLVER factorizations do
-// NOT come through here: they call rocBLAS's internal C++ templates, not these exported C entry points (INTEGRATION.md "What the hook
-// reaches", tests/test_gpu_hook_reach.py).  rocblas_operation / rocblas_status are plain ints here (111 / 112 / 113 = the hipBLAS values;
-// 0 = success, 6 = internal error); rocblas_int is 32-bit in this build of rocBLAS (rocblas-types.h:79).
-}  // extern "C"
-#pragma GCC visibility pop
-namespace {
-void* mapped_rocblas() {
-    static void* h = mapped_library("librocblas.so");
-    return h;
-}
-template <typename Fn> Fn real_rocblas(const char* name) {
-    void* f = dlsym(RTLD_NEXT, name);
-    if (!f)
-        if (void* h = mapped_rocblas()) f = dlsym(h, name);
-    return reinterpret_cast<Fn>(f);
-}
+// declined arrives here again through the real hipBLAS and is declined again by the same rules.  rocblas_operation / rocblas_status are plain
+// ints here (111 / 112 / 113 = the hipBLAS values; 0 = success, 6 = internal error); rocblas_int is 32-bit in this build of rocBLAS
+// (rocblas-types.h:79).
 bool rocblas_stream(void* handle, hipStream_t* s) {
-    using Fn = int (*)(void*, hipStream_t*);
-    static Fn fn = real_rocblas<Fn>("rocblas_get_stream");
+    static const auto fn = real<decltype(&rocblas_get_stream)>("rocblas_get_stream");
     return fn && fn(handle, s) == 0;
 }
 int rocblas_status_of(hipblasStatus_t st) { return st == HIPBLAS_STATUS_SUCCESS ? 0 : st == HIPBLAS_STATUS_ALLOC_FAILED ? 5 : 6; }
@@ -1014,10 +870,8 @@ bool rocblas_version_tested(const char* v) {
 bool rocblas_internal_abi_ok() {
     static const bool ok = [] {
         if (env_one("GEMMUL8_ROCBLAS_ABI_UNCHECKED")) return true;
-        using SizeFn = int (*)(size_t*);
-        using StrFn = int (*)(char*, size_t);
-        SizeFn fsz = real_rocblas<SizeFn>("rocblas_get_version_string_size");
-        StrFn fstr = real_rocblas<StrFn>("rocblas_get_version_string");
+        const auto fsz = real<decltype(&rocblas_get_version_string_size)>("rocblas_get_version_string_size");
+        const auto fstr = real<decltype(&rocblas_get_version_string)>("rocblas_get_version_string");
         char buf[128] = "";
         size_t len = 0;
         const bool have = fsz && fstr && fsz(&len) == 0 && len > 0 && len <= sizeof(buf) && fstr(buf, len) == 0;
@@ -1030,145 +884,38 @@ bool rocblas_internal_abi_ok() {
     }();
     return ok;
 }
-}  // namespace
-extern "C" GEMMUL8_API int gemmul8_hook_rocblas_version_tested(const char* version) { return rocblas_version_tested(version) ? 1 : 0; }
-#pragma GCC visibility push(default)
-extern "C" {
-
-int rocblas_destroy_handle(void* handle) {
-    if (handle) release_state((hipblasHandle_t)handle, true);
-    using Fn = int (*)(void*);
-    static Fn real = real_rocblas<Fn>("rocblas_destroy_handle");
-    NativeScope ns_; return real ? real(handle) : 6;
+// What every rocBLAS entry point asks once the call itself is one for the emulator (gemm_call): the opt-in switch, for the internal
+// template the tested release, operations the emulator knows, and -- last, only after all the cheaper tests -- the handle's stream.
+bool rocblas_takes(void* handle, int transA, int transB, hipStream_t* s, bool internal_template = false) {
+    return env_one("GEMMUL8_HOOK_ROCBLAS") && (!internal_template || rocblas_internal_abi_ok()) && handle && transA >= 111 && transA <= 113 &&
+           transB >= 111 && transB <= 113 && rocblas_stream(handle, s);
 }
 
-#define OZ2_ROCBLAS_GEMM_HOOK(NAME, T, CODE)                                                                                             \
-    int NAME(void* handle, int transA, int transB, int m, int n, int k, const T* alpha, const T* A, int lda, const T* B, int ldb,        \
-             const T* beta, T* C, int ldc) {                                                                                             \
-        using Fn = int (*)(void*, int, int, int, int, int, const T*, const T*, int, const T*, int, const T*, T*, int);                   \
-        static Fn real = real_rocblas<Fn>(#NAME);                                                                                        \
-        hipStream_t s_;                                                                                                                  \
-        hipblasStatus_t st_;                                                                                                             \
-        if (env_one("GEMMUL8_HOOK_ROCBLAS") && handle && m > 0 && n > 0 && k > 0 && alpha && A && B && beta && C &&                      \
-            transA >= 111 && transA <= 113 && transB >= 111 && transB <= 113 && rocblas_stream(handle, &s_) &&                           \
-            try_emulate(CODE, (hipblasHandle_t)handle, (hipblasOperation_t)transA, (hipblasOperation_t)transB, m, n, k, alpha, A, lda, B, \
-                        ldb, beta, C, ldc, &st_, &s_))                                                                                   \
-            return rocblas_status_of(st_);                                                                                               \
-        NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc) : 6;                                    \
-    }
-OZ2_ROCBLAS_GEMM_HOOK(rocblas_sgemm, float, GEMMUL8_S)
-OZ2_ROCBLAS_GEMM_HOOK(rocblas_dgemm, double, GEMMUL8_D)
-OZ2_ROCBLAS_GEMM_HOOK(rocblas_cgemm, hipComplex, GEMMUL8_C)
-OZ2_ROCBLAS_GEMM_HOOK(rocblas_zgemm, hipDoubleComplex, GEMMUL8_Z)
-#undef OZ2_ROCBLAS_GEMM_HOOK
-
-#define OZ2_ROCBLAS_SB_HOOK(NAME, T, CODE)                                                                                               \
-    int NAME(void* handle, int transA, int transB, int m, int n, int k, const T* alpha, const T* A, int lda, long long strideA,          \
-             const T* B, int ldb, long long strideB, const T* beta, T* C, int ldc, long long strideC, int batchCount) {                  \
-        using Fn = int (*)(void*, int, int, int, int, int, const T*, const T*, int, long long, const T*, int, long long, const T*, T*,   \
-                           int, long long, int);                                                                                         \
-        static Fn real = real_rocblas<Fn>(#NAME);                                                                                        \
-        hipStream_t s_;                                                                                                                  \
-        hipblasStatus_t st_;                                                                                                             \
-        if (env_one("GEMMUL8_HOOK_ROCBLAS") && handle && m > 0 && n > 0 && k > 0 && batchCount > 0 && alpha && A && B && beta && C &&    \
-            transA >= 111 && transA <= 113 && transB >= 111 && transB <= 113 && rocblas_stream(handle, &s_) &&                           \
-            emulate_batch(CODE, sizeof(T), (hipblasHandle_t)handle, (hipblasOperation_t)transA, (hipblasOperation_t)transB, m, n, k,     \
-                          alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batchCount, &st_, &s_))                        \
-            return rocblas_status_of(st_);                                                                                               \
-        NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batchCount) : 6; \
-    }
-OZ2_ROCBLAS_SB_HOOK(rocblas_sgemm_strided_batched, float, GEMMUL8_S)
-OZ2_ROCBLAS_SB_HOOK(rocblas_dgemm_strided_batched, double, GEMMUL8_D)
-OZ2_ROCBLAS_SB_HOOK(rocblas_cgemm_strided_batched, hipComplex, GEMMUL8_C)
-OZ2_ROCBLAS_SB_HOOK(rocblas_zgemm_strided_batched, hipDoubleComplex, GEMMUL8_Z)
-#undef OZ2_ROCBLAS_SB_HOOK
-
-// rocSOLVER / hipSOLVER factorizations (getrf, geqrf, potrf ...: what torch.linalg.lu_factor / solve / qr run on) do not call the C entry
-// points above: their trailing updates go through rocBLAS's exported C++ template rocblas_internal_gemm_template<T> (and its _64 form).
+// rocSOLVER / hipSOLVER factorizations (getrf, geqrf, potrf ...: what torch.linalg.lu_factor / solve / qr run on) do not call rocBLAS's C
+// entry points: their trailing updates go through rocBLAS's exported C++ template rocblas_internal_gemm_template<T> (and its _64 form).
 // Those ARE dynamic symbols, so the same opt-in interposes them -- by their mangled names, which belong to THIS rocBLAS ABI (ROCm 7.2:
 // nm -D librocsolver.so | grep internal_gemm); if a later rocBLAS changes the signature the names no longer match, nothing is intercepted,
 // and tests/test_gpu_hook_reach.py says so.  Strided batch (batch_count > 1) and element offsets as rocBLAS defines them.
-}  // extern "C"
-template <typename T, typename I>
-static int rocblas_internal_gemm_hook(const char* mangled, int code, void* handle, int transA, int transB, I m, I n, I k, const T* alpha, const T* A,
-                                      long offA, I lda, long strideA, const T* B, long offB, I ldb, long strideB, const T* beta, T* C, long offC,
-                                      I ldc, long strideC, I batch) {
-    using Fn = int (*)(void*, int, int, I, I, I, const T*, const T*, long, I, long, const T*, long, I, long, const T*, T*, long, I, long, I);
-    static Fn real = real_rocblas<Fn>(mangled);  // one symbol per <T, I> instantiation: resolved once
+// real_: the routine behind the mangled name, one per <T, I>, resolved once by the caller.
+template <typename T, typename I, typename Fn>
+int rocblas_internal_gemm_hook(Fn real_, int code, void* handle, int transA, int transB, I m, I n, I k, const T* alpha, const T* A, long offA, I lda,
+                               long strideA, const T* B, long offB, I ldb, long strideB, const T* beta, T* C, long offC, I ldc, long strideC, I batch) {
+    GemmCall c;
     hipStream_t s_;
     hipblasStatus_t st_;
-    const bool fits = m > 0 && n > 0 && k > 0 && batch > 0 && (long long)m <= 2147483647 && (long long)n <= 2147483647 && (long long)k <= 2147483647 &&
-                      (long long)lda <= 2147483647 && (long long)ldb <= 2147483647 && (long long)ldc <= 2147483647 && (long long)batch <= 2147483647;
-    if (fits && env_one("GEMMUL8_HOOK_ROCBLAS") && rocblas_internal_abi_ok() && handle && alpha && A && B && beta && C && transA >= 111 && transA <= 113 &&
-        transB >= 111 && transB <= 113 && rocblas_stream(handle, &s_)) {
-        const T *Ao = A + offA, *Bo = B + offB;
-        T* Co = C + offC;
-        const bool served = batch == 1 ? try_emulate(code, (hipblasHandle_t)handle, (hipblasOperation_t)transA, (hipblasOperation_t)transB, (int)m, (int)n,
-                                                     (int)k, alpha, Ao, (int)lda, Bo, (int)ldb, beta, Co, (int)ldc, &st_, &s_)
-                                       : emulate_batch(code, sizeof(T), (hipblasHandle_t)handle, (hipblasOperation_t)transA, (hipblasOperation_t)transB,
-                                                       (int)m, (int)n, (int)k, alpha, Ao, (int)lda, strideA, Bo, (int)ldb, strideB, beta, Co, (int)ldc,
-                                                       strideC, (int)batch, &st_, &s_);
-        if (served) return rocblas_status_of(st_);
-    }
-    NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, A, offA, lda, strideA, B, offB, ldb, strideB, beta, C, offC, ldc, strideC, batch) : 6;
-}
-extern "C" {
-#define OZ2_ROCBLAS_INTERNAL(FN, T, CODE, SYM32, SYM64)                                                                                   \
-    int FN##_32(void* h, int ta, int tb, int m, int n, int k, const T* al, const T* A, long oa, int lda, long sa, const T* B, long ob, int ldb, \
-                long sb, const T* be, T* C, long oc, int ldc, long sc, int bc) __asm__(SYM32);                                            \
-    int FN##_32(void* h, int ta, int tb, int m, int n, int k, const T* al, const T* A, long oa, int lda, long sa, const T* B, long ob, int ldb, \
-                long sb, const T* be, T* C, long oc, int ldc, long sc, int bc) {                                                          \
-        return rocblas_internal_gemm_hook<T, int>(SYM32, CODE, h, ta, tb, m, n, k, al, A, oa, lda, sa, B, ob, ldb, sb, be, C, oc, ldc, sc, bc); \
-    }                                                                                                                                     \
-    int FN##_64(void* h, int ta, int tb, long m, long n, long k, const T* al, const T* A, long oa, long lda, long sa, const T* B, long ob,  \
-                long ldb, long sb, const T* be, T* C, long oc, long ldc, long sc, long bc) __asm__(SYM64);                                \
-    int FN##_64(void* h, int ta, int tb, long m, long n, long k, const T* al, const T* A, long oa, long lda, long sa, const T* B, long ob,  \
-                long ldb, long sb, const T* be, T* C, long oc, long ldc, long sc, long bc) {                                              \
-        return rocblas_internal_gemm_hook<T, long>(SYM64, CODE, h, ta, tb, m, n, k, al, A, oa, lda, sa, B, ob, ldb, sb, be, C, oc, ldc, sc, bc); \
-    }
-OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_s, float, GEMMUL8_S,
-                     "_Z30rocblas_internal_gemm_templateIfE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_iiiPKT_S6_lilS6_lilS6_PS4_lili",
-                     "_Z33rocblas_internal_gemm_template_64IfE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_lllPKT_S6_lllS6_lllS6_PS4_llll")
-OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_d, double, GEMMUL8_D,
-                     "_Z30rocblas_internal_gemm_templateIdE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_iiiPKT_S6_lilS6_lilS6_PS4_lili",
-                     "_Z33rocblas_internal_gemm_template_64IdE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_lllPKT_S6_lllS6_lllS6_PS4_llll")
-OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_c, hipComplex, GEMMUL8_C,
-                     "_Z30rocblas_internal_gemm_templateI19rocblas_complex_numIfEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_iiiPKT_S8_lilS8_lilS8_PS6_lili",
-                     "_Z33rocblas_internal_gemm_template_64I19rocblas_complex_numIfEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_lllPKT_S8_lllS8_lllS8_PS6_llll")
-OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_z, hipDoubleComplex, GEMMUL8_Z,
-                     "_Z30rocblas_internal_gemm_templateI19rocblas_complex_numIdEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_iiiPKT_S8_lilS8_lilS8_PS6_lili",
-                     "_Z33rocblas_internal_gemm_template_64I19rocblas_complex_numIdEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_lllPKT_S8_lllS8_lllS8_PS6_llll")
-#undef OZ2_ROCBLAS_INTERNAL
-
-// rocblas_gemm_ex: D = alpha op(A) op(B) + beta C.  Emulated for the four plain types (all of a / b / c / d / compute the same type) when it
-// is the in-place form (c == d, ldc == ldd) -- what rocBLAS's own clients and hipBLAS's GemmEx issue; anything else goes to rocBLAS.
-int rocblas_gemm_ex(void* handle, int transA, int transB, int m, int n, int k, const void* alpha, const void* a, int a_type, int lda,
-                    const void* b, int b_type, int ldb, const void* beta, const void* c, int c_type, int ldc, void* d, int d_type, int ldd,
-                    int compute_type, int algo, int32_t solution_index, uint32_t flags) {
-    using Fn = int (*)(void*, int, int, int, int, int, const void*, const void*, int, int, const void*, int, int, const void*, const void*, int,
-                       int, void*, int, int, int, int, int32_t, uint32_t);
-    static Fn real = real_rocblas<Fn>("rocblas_gemm_ex");
-    const bool same = a_type == b_type && b_type == c_type && c_type == d_type && d_type == compute_type;
-    const int dtype = !same ? -1 : a_type == 151 ? GEMMUL8_S : a_type == 152 ? GEMMUL8_D : a_type == 154 ? GEMMUL8_C : a_type == 155 ? GEMMUL8_Z : -1;
-    hipStream_t s_;
-    hipblasStatus_t st_;
-    if (dtype >= 0 && env_one("GEMMUL8_HOOK_ROCBLAS") && handle && m > 0 && n > 0 && k > 0 && alpha && a && b && beta && d && c == d &&
-        ldc == ldd && transA >= 111 && transA <= 113 && transB >= 111 && transB <= 113 && rocblas_stream(handle, &s_) &&
-        try_emulate(dtype, (hipblasHandle_t)handle, (hipblasOperation_t)transA, (hipblasOperation_t)transB, m, n, k, alpha, a, lda, b, ldb, beta,
-                    d, ldd, &st_, &s_))
+    if (gemm_call(&c, code, transA, transB, m, n, k, alpha, A ? A + offA : A, lda, strideA, B ? B + offB : B, ldb, strideB, beta, C ? C + offC : C, ldc,
+                  strideC, batch) &&
+        alpha && beta && rocblas_takes(handle, transA, transB, &s_, true) &&
+        (c.batch == 1 ? try_emulate(handle, c, &st_, &s_) : emulate_batch(handle, c, &st_, &s_)))
         return rocblas_status_of(st_);
-    NativeScope ns_; return real ? real(handle, transA, transB, m, n, k, alpha, a, a_type, lda, b, b_type, ldb, beta, c, c_type, ldc, d, d_type, ldd, compute_type,
-                       algo, solution_index, flags)
-                : 6;
+    NativeScope ns_;
+    return real_ ? real_(handle, transA, transB, m, n, k, alpha, A, offA, lda, strideA, B, offB, ldb, strideB, beta, C, offC, ldc, strideC, batch) : 6;
 }
-}  // extern "C"
 
 // ---- hipblasLtMatmul (not hooked by the reference; PyTorch on ROCm routes most float32 matmuls through hipBLASLt, so without
 // this GEMMUL8_NUM_MOD_S is a no-op for them).  Only the plain case is emulated: D = alpha*op(A)*op(B) + beta*C with A, B, C, D of
 // one type in {float, double, complex float, complex double}, column-major order, single or strided-batched, default epilogue, no scale pointers,
 // host or device scalars; everything else goes to the real routine untouched.  C != D is served in place on D after a copy of C.
-#include <hipblaslt/hipblaslt.h>
-namespace {
 struct LtLayout {
     int32_t type = -1, order = -1, batch = 1;
     uint64_t rows = 0, cols = 0;
@@ -1197,8 +944,7 @@ bool lt_try(hipblasLtHandle_t handle, hipblasLtMatmulDesc_t desc, const void* al
             hipblasLtMatrixLayout_t Bd, const void* beta, const void* C, hipblasLtMatrixLayout_t Cd, void* D, hipblasLtMatrixLayout_t Dd,
             hipStream_t stream, hipblasStatus_t* st) {
     if (!desc || !alpha || !beta || !A || !B || !D) return lt_decline("null argument");
-    using DescGet = hipblasStatus_t (*)(hipblasLtMatmulDesc_t, hipblasLtMatmulDescAttributes_t, void*, size_t, size_t*);
-    static DescGet dget = real_fn<DescGet>("hipblasLtMatmulDescGetAttribute");
+    static const auto dget = real<decltype(&hipblasLtMatmulDescGetAttribute)>("hipblasLtMatmulDescGetAttribute");
     if (!dget) return lt_decline("hipblasLtMatmulDescGetAttribute not found");
     size_t w = 0;
     int32_t ta = 0, tb = 0;
@@ -1229,14 +975,8 @@ bool lt_try(hipblasLtHandle_t handle, hipblasLtMatmulDesc_t desc, const void* al
     if (haveC && !lt_layout(Cd, &c)) return lt_decline("the C layout was not created under the hook");
     if (!haveC) c = d;
     if (a.type != b.type || a.type != d.type || c.type != d.type) return lt_decline("mixed matrix types");
-    int dtype = -1;
-    switch (a.type) {
-    case HIP_R_32F: dtype = GEMMUL8_S; break;
-    case HIP_R_64F: dtype = GEMMUL8_D; break;
-    case HIP_C_32F: dtype = GEMMUL8_C; break;
-    case HIP_C_64F: dtype = GEMMUL8_Z; break;
-    default: return lt_decline("not an S/D/C/Z matrix type");
-    }
+    const int dtype = dtype_of(a.type);
+    if (dtype < 0) return lt_decline("not an S/D/C/Z matrix type");
     if (bias) {
         int32_t bt = a.type;
         // an unset BIAS_DATA_TYPE reads back as 255 (invalid) in ROCm 7.2 and means "the type of D"
@@ -1253,27 +993,22 @@ bool lt_try(hipblasLtHandle_t handle, hipblasLtMatmulDesc_t desc, const void* al
     if ((ta == HIPBLAS_OP_N ? a.rows : a.cols) != m || (tb == HIPBLAS_OP_N ? b.cols : b.rows) != n || (tb == HIPBLAS_OP_N ? b.rows : b.cols) != k)
         return lt_decline("inconsistent dimensions");
     if (c.rows != m || c.cols != n || m == 0 || n == 0 || k == 0) return lt_decline("C / D shape");
-    if (!fits_int((int64_t)m, (int64_t)n, (int64_t)k, a.ld, b.ld, d.ld) || c.ld > 2147483647) return false;
-    const size_t esz = dtype == GEMMUL8_S ? 4 : dtype == GEMMUL8_Z ? 16 : 8;
-    // cheap env test before touching D: is emulation selected for this type at all?
-    const unsigned N = (unsigned)env_u64(kTypes[dtype].nmod, 0);
-    if (N < 2u || N > kTypes[dtype].max_moduli) return false;
-    if (below_floor(dtype, (double)m, (double)n, (double)k, N, env_one(kTypes[dtype].fast), env_backend("GEMMUL8_BACKEND", 0, false), (double)nb)) return false;
-    if (k > (1u << 17) || (env_backend("GEMMUL8_BACKEND", 0, false) == 1 && k > 65536)) return false;  // outside the emulator's range
+    GemmCall g;
+    if (!gemm_call(&g, dtype, ta, tb, (int64_t)m, (int64_t)n, (int64_t)k, alpha, A, a.ld, a.stride, B, b.ld, b.stride, beta, D, d.ld, d.stride, nb) ||
+        c.ld > 2147483647)
+        return false;
+    const size_t esz = g.elem;
+    // cheap env test before touching D: is emulation selected for this call at all, and is it one the emulator takes?
+    Selection s;
+    if (!selected(g, &s) || !k_in_range(g, s)) return false;
     // C is not read when the host scalar beta is 0 (the CRT's "C = +-AB" forms and its general form with beta == 0, oz2_crt.hip): then
     // the out-of-place form needs no copy of C into D.  Device scalars: beta is unknown here, C is copied (the kernel still skips
     // reading it when *beta == 0).
     bool c_unread = false;
     if (pmode == HIPBLASLT_POINTER_MODE_HOST) {
-        double ar, ai = 0, br, bi2 = 0;
-        if (dtype == GEMMUL8_S || dtype == GEMMUL8_C) {
-            ar = ((const float*)alpha)[0], br = ((const float*)beta)[0];
-            if (dtype == GEMMUL8_C) ai = ((const float*)alpha)[1], bi2 = ((const float*)beta)[1];
-        } else {
-            ar = ((const double*)alpha)[0], br = ((const double*)beta)[0];
-            if (dtype == GEMMUL8_Z) ai = ((const double*)alpha)[1], bi2 = ((const double*)beta)[1];
-        }
-        (void)ar, (void)ai;
+        const bool single = dtype == GEMMUL8_S || dtype == GEMMUL8_C;
+        const double br = single ? ((const float*)beta)[0] : ((const double*)beta)[0];
+        const double bi2 = !kTypes[dtype].cplx ? 0 : single ? ((const float*)beta)[1] : ((const double*)beta)[1];
         c_unread = br == 0 && bi2 == 0;
     }
     if (haveC && C != D && !c_unread) {  // out-of-place form: bring C into D, then update D in place
@@ -1284,22 +1019,179 @@ bool lt_try(hipblasLtHandle_t handle, hipblasLtMatmulDesc_t desc, const void* al
                 return *st = HIPBLAS_STATUS_INTERNAL_ERROR, true;
     }
     if (nb > 1)  // strided batch (torch.bmm in float32 arrives here): one set of launches, as for hipblas*gemmStridedBatched
-        return emulate_batch(dtype, esz, (hipblasHandle_t)handle, (hipblasOperation_t)ta, (hipblasOperation_t)tb, (int)m, (int)n, (int)k, alpha, A,
-                             (int)a.ld, (long long)a.stride, B, (int)b.ld, (long long)b.stride, beta, D, (int)d.ld, (long long)d.stride, nb, st, &stream);
-    const bool done = try_emulate(dtype, (hipblasHandle_t)handle, (hipblasOperation_t)ta, (hipblasOperation_t)tb, (int)m, (int)n, (int)k, alpha, A,
-                                  (int)a.ld, B, (int)b.ld, beta, D, (int)d.ld, st, &stream);
+        return emulate_batch((hipblasHandle_t)handle, g, st, &stream);
+    const bool done = try_emulate((hipblasHandle_t)handle, g, st, &stream);
     if (done && bias && *st == HIPBLAS_STATUS_SUCCESS &&
-        gemmul8_add_row_bias(stream, dtype, (size_t)m, (size_t)n, D, (size_t)d.ld, bias) != 0)
+        abi().add_row_bias(stream, dtype, (size_t)m, (size_t)n, D, (size_t)d.ld, bias) != 0)
         *st = HIPBLAS_STATUS_INTERNAL_ERROR;
     return done;
 }
+
+// the plain GEMM entry points' contract (hook.cu:616-617): true = answered here, with *st
+bool plain_gemm(hipblasHandle_t handle, int dtype, hipblasOperation_t ta, hipblasOperation_t tb, int64_t m, int64_t n, int64_t k, const void* alpha,
+                const void* A, int64_t lda, const void* B, int64_t ldb, const void* beta, void* C, int64_t ldc, hipblasStatus_t* st) {
+    if (m <= 0 || n <= 0 || k <= 0) return *st = HIPBLAS_STATUS_SUCCESS, true;
+    if (!A || !B || !C) return *st = HIPBLAS_STATUS_INVALID_VALUE, true;
+    GemmCall c;
+    return gemm_call(&c, dtype, ta, tb, m, n, k, alpha, A, lda, 0, B, ldb, 0, beta, C, ldc, 0) && try_emulate(handle, c, st);
+}
+// Strided-batched entry points (not hooked by the reference; PyTorch's bmm uses them): no early out -- a degenerate or null argument is
+// the native routine's to answer.  alpha / beta are shared by the batch; element strides are in units of the matrix type.
+bool batched_gemm(hipblasHandle_t handle, int dtype, hipblasOperation_t ta, hipblasOperation_t tb, int m, int n, int k, const void* alpha, const void* A,
+                  int lda, long long sa, const void* B, int ldb, long long sb, const void* beta, void* C, int ldc, long long sc, int batch,
+                  hipblasStatus_t* st) {
+    GemmCall c;
+    return gemm_call(&c, dtype, ta, tb, m, n, k, alpha, A, lda, sa, B, ldb, sb, beta, C, ldc, sc, batch) && alpha && beta && emulate_batch(handle, c, st);
+}
+
 }  // namespace
 
-extern "C" hipblasStatus_t hipblasLtMatrixLayoutCreate(hipblasLtMatrixLayout_t* matLayout, hipDataType type, uint64_t rows, uint64_t cols, int64_t ld) {
-    using Fn = hipblasStatus_t (*)(hipblasLtMatrixLayout_t*, hipDataType, uint64_t, uint64_t, int64_t);
-    static Fn real = real_fn<Fn>("hipblasLtMatrixLayoutCreate");
-    if (!real) return HIPBLAS_STATUS_NOT_INITIALIZED;
-    const hipblasStatus_t st = real(matLayout, type, rows, cols, ld);
+// ---- the exported symbols: everything above is local to this file, everything below has default visibility
+#pragma GCC visibility push(default)
+extern "C" {
+
+int gemmul8_hook_would_emulate(int dtype, int backend, size_t m, size_t n, size_t k, unsigned num_moduli, int fastmode, size_t batch) {
+    if (dtype < 0 || dtype > 3 || (backend != GEMMUL8_INT8 && backend != GEMMUL8_FP8) || batch == 0 || num_moduli < 2 ||
+        num_moduli > kTypes[dtype].max_moduli)
+        return GEMMUL8_E_ARG;
+    if (m == 0 || n == 0 || k == 0) return 0;
+    return below_floor(dtype, (double)m, (double)n, (double)k, num_moduli, fastmode != 0, backend, (double)batch, true) ? 0 : 1;
+}
+int gemmul8_hook_rocblas_version_tested(const char* version) { return rocblas_version_tested(version) ? 1 : 0; }
+
+hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
+    release_state(handle);
+    OZ2_NATIVE(hipblasDestroy, HIPBLAS_STATUS_NOT_INITIALIZED, handle);
+}
+
+// I = int, or int64_t for the ILP64 twins of ROCm 7: the same emulation when every dimension fits an int, the native routine otherwise
+#define OZ2_GEMM_HOOK(NAME, T, I, CODE)                                                                                                 \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, I m, I n, I k, const T* alpha,   \
+                         const T* A, I lda, const T* B, I ldb, const T* beta, T* C, I ldc) {                                            \
+        hipblasStatus_t st;                                                                                                             \
+        if (plain_gemm(handle, CODE, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;                     \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);         \
+    }
+#define OZ2_SB_HOOK(NAME, T, CODE)                                                                                                      \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int m, int n, int k,              \
+                         const T* alpha, const T* A, int lda, long long strideA, const T* B, int ldb, long long strideB, const T* beta, \
+                         T* C, int ldc, long long strideC, int batchCount) {                                                            \
+        hipblasStatus_t st;                                                                                                             \
+        if (batched_gemm(handle, CODE, transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC,         \
+                         batchCount, &st))                                                                                              \
+            return st;                                                                                                                  \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB,      \
+                   beta, C, ldc, strideC, batchCount);                                                                                  \
+    }
+// the trailing argument, if any, is the `flags` of the WithFlags forms
+#define OZ2_GEMM_EX_HOOK(NAME, I, ...)                                                                                                  \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, I m, I n, I k, const void* alpha, \
+                         const void* A, hipDataType aType, I lda, const void* B, hipDataType bType, I ldb, const void* beta, void* C,   \
+                         hipDataType cType, I ldc, hipblasComputeType_t computeType,                                                    \
+                         hipblasGemmAlgo_t algo __VA_OPT__(, hipblasGemmFlags_t) __VA_ARGS__) {                                         \
+        hipblasStatus_t st;                                                                                                             \
+        if (plain_gemm(handle, dtype_of(aType, bType, cType, computeType), transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C,     \
+                       ldc, &st))                                                                                                       \
+            return st;                                                                                                                  \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, transA, transB, m, n, k, alpha, A, aType, lda, B, bType, ldb, beta, C, \
+                   cType, ldc, computeType, algo __VA_OPT__(, ) __VA_ARGS__);                                                           \
+    }
+// the rocBLAS C entry points: act only with GEMMUL8_HOOK_ROCBLAS=1 (rocblas_takes)
+#define OZ2_ROCBLAS_HOOK(NAME, SB_NAME, T, CODE)                                                                                        \
+    int NAME(void* handle, int transA, int transB, int m, int n, int k, const T* alpha, const T* A, int lda, const T* B, int ldb,       \
+             const T* beta, T* C, int ldc) {                                                                                            \
+        GemmCall c;                                                                                                                     \
+        hipStream_t s_;                                                                                                                 \
+        hipblasStatus_t st_;                                                                                                            \
+        if (gemm_call(&c, CODE, transA, transB, m, n, k, alpha, A, lda, 0, B, ldb, 0, beta, C, ldc, 0) && alpha && beta &&              \
+            rocblas_takes(handle, transA, transB, &s_) && try_emulate(handle, c, &st_, &s_))                                            \
+            return rocblas_status_of(st_);                                                                                              \
+        OZ2_NATIVE(NAME, 6, handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);                                      \
+    }                                                                                                                                   \
+    int SB_NAME(void* handle, int transA, int transB, int m, int n, int k, const T* alpha, const T* A, int lda, long long strideA,      \
+                const T* B, int ldb, long long strideB, const T* beta, T* C, int ldc, long long strideC, int batchCount) {              \
+        GemmCall c;                                                                                                                     \
+        hipStream_t s_;                                                                                                                 \
+        hipblasStatus_t st_;                                                                                                            \
+        if (gemm_call(&c, CODE, transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batchCount) && \
+            alpha && beta && rocblas_takes(handle, transA, transB, &s_) && emulate_batch(handle, c, &st_, &s_))                         \
+            return rocblas_status_of(st_);                                                                                              \
+        OZ2_NATIVE(SB_NAME, 6, handle, transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC,         \
+                   batchCount);                                                                                                         \
+    }
+// rocblas_internal_gemm_template<T> (I = int) and rocblas_internal_gemm_template_64<T> (I = long) under their mangled names
+#define OZ2_ROCBLAS_INTERNAL(FN, T, I, CODE, SYM)                                                                                       \
+    int FN(void* h, int ta, int tb, I m, I n, I k, const T* al, const T* A, long oa, I lda, long sa, const T* B, long ob, I ldb, long sb, \
+           const T* be, T* C, long oc, I ldc, long sc, I bc) __asm__(SYM);                                                              \
+    int FN(void* h, int ta, int tb, I m, I n, I k, const T* al, const T* A, long oa, I lda, long sa, const T* B, long ob, I ldb, long sb, \
+           const T* be, T* C, long oc, I ldc, long sc, I bc) {                                                                          \
+        static const auto real_ = real<decltype(&FN)>(SYM);                                                                             \
+        return rocblas_internal_gemm_hook<T, I>(real_, CODE, h, ta, tb, m, n, k, al, A, oa, lda, sa, B, ob, ldb, sb, be, C, oc, ldc, sc, bc); \
+    }
+// one stamp per type; Z / ZZ: the substitution indices of the mangled names, which differ between the real and the complex forms
+#define OZ2_TYPE_HOOKS(L, U, T, CODE, TAG, Z, ZZ, ZZZ)                                                                                   \
+    OZ2_GEMM_HOOK(hipblas##U##gemm, T, int, CODE)                                                                                       \
+    OZ2_GEMM_HOOK(hipblas##U##gemm_64, T, int64_t, CODE)                                                                                \
+    OZ2_SB_HOOK(hipblas##U##gemmStridedBatched, T, CODE)                                                                                \
+    OZ2_ROCBLAS_HOOK(rocblas_##L##gemm, rocblas_##L##gemm_strided_batched, T, CODE)                                                     \
+    OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_##L##_32, T, int, CODE,                                                                        \
+                         "_Z30rocblas_internal_gemm_templateI" TAG "E15rocblas_status_P15_rocblas_handle18rocblas_operation_" Z         \
+                         "_iiiPKT_" ZZ "_lil" ZZ "_lil" ZZ "_P" ZZZ "_lili")                                                            \
+    OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_##L##_64, T, long, CODE,                                                                       \
+                         "_Z33rocblas_internal_gemm_template_64I" TAG "E15rocblas_status_P15_rocblas_handle18rocblas_operation_" Z      \
+                         "_lllPKT_" ZZ "_lll" ZZ "_lll" ZZ "_P" ZZZ "_llll")
+OZ2_TYPE_HOOKS(s, S, float, GEMMUL8_S, "f", "S3", "S6", "S4")
+OZ2_TYPE_HOOKS(d, D, double, GEMMUL8_D, "d", "S3", "S6", "S4")
+OZ2_TYPE_HOOKS(c, C, hipComplex, GEMMUL8_C, "19rocblas_complex_numIfE", "S5", "S8", "S6")
+OZ2_TYPE_HOOKS(z, Z, hipDoubleComplex, GEMMUL8_Z, "19rocblas_complex_numIdE", "S5", "S8", "S6")
+OZ2_GEMM_EX_HOOK(hipblasGemmEx, int)
+OZ2_GEMM_EX_HOOK(hipblasGemmEx_64, int64_t)
+OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags, int, flags)
+OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
+#undef OZ2_TYPE_HOOKS
+#undef OZ2_ROCBLAS_INTERNAL
+#undef OZ2_ROCBLAS_HOOK
+#undef OZ2_GEMM_EX_HOOK
+#undef OZ2_SB_HOOK
+#undef OZ2_GEMM_HOOK
+
+hipblasStatus_t hipblasGemmStridedBatchedEx(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, int m, int n, int k,
+                                            const void* alpha, const void* A, hipDataType aType, int lda, hipblasStride strideA, const void* B,
+                                            hipDataType bType, int ldb, hipblasStride strideB, const void* beta, void* C, hipDataType cType,
+                                            int ldc, hipblasStride strideC, int batchCount, hipblasComputeType_t computeType,
+                                            hipblasGemmAlgo_t algo) {
+    hipblasStatus_t st;
+    if (batched_gemm(handle, dtype_of(aType, bType, cType, computeType), transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc,
+                     strideC, batchCount, &st))
+        return st;
+    OZ2_NATIVE(hipblasGemmStridedBatchedEx, HIPBLAS_STATUS_NOT_INITIALIZED, handle, transA, transB, m, n, k, alpha, A, aType, lda, strideA, B, bType, ldb,
+               strideB, beta, C, cType, ldc, strideC, batchCount, computeType, algo);
+}
+
+int rocblas_destroy_handle(void* handle) {
+    if (handle) release_state((hipblasHandle_t)handle, true);
+    OZ2_NATIVE(rocblas_destroy_handle, 6, handle);
+}
+// rocblas_gemm_ex: D = alpha op(A) op(B) + beta C.  Emulated for the four plain types (all of a / b / c / d / compute the same type) when it
+// is the in-place form (c == d, ldc == ldd) -- what rocBLAS's own clients and hipBLAS's GemmEx issue; anything else goes to rocBLAS.
+int rocblas_gemm_ex(void* handle, int transA, int transB, int m, int n, int k, const void* alpha, const void* a, int a_type, int lda,
+                    const void* b, int b_type, int ldb, const void* beta, const void* c, int c_type, int ldc, void* d, int d_type, int ldd,
+                    int compute_type, int algo, int32_t solution_index, uint32_t flags) {
+    const bool same = a_type == b_type && b_type == c_type && c_type == d_type && d_type == compute_type;
+    GemmCall g;
+    hipStream_t s_;
+    hipblasStatus_t st_;
+    if (same && c == d && ldc == ldd && gemm_call(&g, dtype_of_rocblas(a_type), transA, transB, m, n, k, alpha, a, lda, 0, b, ldb, 0, beta, d, ldd, 0) &&
+        alpha && beta && rocblas_takes(handle, transA, transB, &s_) && try_emulate(handle, g, &st_, &s_))
+        return rocblas_status_of(st_);
+    OZ2_NATIVE(rocblas_gemm_ex, 6, handle, transA, transB, m, n, k, alpha, a, a_type, lda, b, b_type, ldb, beta, c, c_type, ldc, d, d_type, ldd, compute_type,
+               algo, solution_index, flags);
+}
+
+hipblasStatus_t hipblasLtMatrixLayoutCreate(hipblasLtMatrixLayout_t* matLayout, hipDataType type, uint64_t rows, uint64_t cols, int64_t ld) {
+    OZ2_REAL(hipblasLtMatrixLayoutCreate);
+    if (!real_) return HIPBLAS_STATUS_NOT_INITIALIZED;
+    const hipblasStatus_t st = real_(matLayout, type, rows, cols, ld);
     if (st == HIPBLAS_STATUS_SUCCESS && matLayout && *matLayout) {
         LtLayout rec;
         rec.type = (int32_t)type, rec.order = HIPBLASLT_ORDER_COL, rec.batch = 1, rec.rows = rows, rec.cols = cols, rec.ld = ld;
@@ -1308,12 +1200,11 @@ extern "C" hipblasStatus_t hipblasLtMatrixLayoutCreate(hipblasLtMatrixLayout_t* 
     }
     return st;
 }
-extern "C" hipblasStatus_t hipblasLtMatrixLayoutSetAttribute(hipblasLtMatrixLayout_t matLayout, hipblasLtMatrixLayoutAttribute_t attr, const void* buf,
-                                                             size_t sizeInBytes) {
-    using Fn = hipblasStatus_t (*)(hipblasLtMatrixLayout_t, hipblasLtMatrixLayoutAttribute_t, const void*, size_t);
-    static Fn real = real_fn<Fn>("hipblasLtMatrixLayoutSetAttribute");
-    if (!real) return HIPBLAS_STATUS_NOT_INITIALIZED;
-    const hipblasStatus_t st = real(matLayout, attr, buf, sizeInBytes);
+hipblasStatus_t hipblasLtMatrixLayoutSetAttribute(hipblasLtMatrixLayout_t matLayout, hipblasLtMatrixLayoutAttribute_t attr, const void* buf,
+                                                  size_t sizeInBytes) {
+    OZ2_REAL(hipblasLtMatrixLayoutSetAttribute);
+    if (!real_) return HIPBLAS_STATUS_NOT_INITIALIZED;
+    const hipblasStatus_t st = real_(matLayout, attr, buf, sizeInBytes);
     if (st == HIPBLAS_STATUS_SUCCESS && buf) {
         std::lock_guard<std::mutex> g(g_lt_mtx);
         auto it = g_lt_layouts.find(matLayout);
@@ -1333,35 +1224,27 @@ extern "C" hipblasStatus_t hipblasLtMatrixLayoutSetAttribute(hipblasLtMatrixLayo
     }
     return st;
 }
-extern "C" hipblasStatus_t hipblasLtMatrixLayoutDestroy(const hipblasLtMatrixLayout_t matLayout) {
+hipblasStatus_t hipblasLtMatrixLayoutDestroy(const hipblasLtMatrixLayout_t matLayout) {
     {
         std::lock_guard<std::mutex> g(g_lt_mtx);
         g_lt_layouts.erase(matLayout);
     }
-    using Fn = hipblasStatus_t (*)(const hipblasLtMatrixLayout_t);
-    static Fn real = real_fn<Fn>("hipblasLtMatrixLayoutDestroy");
-    NativeScope ns_; return real ? real(matLayout) : HIPBLAS_STATUS_NOT_INITIALIZED;
+    OZ2_NATIVE(hipblasLtMatrixLayoutDestroy, HIPBLAS_STATUS_NOT_INITIALIZED, matLayout);
 }
-
 // the per-handle state of an hipblasLt handle is released with the handle, as for hipblasDestroy
-extern "C" hipblasStatus_t hipblasLtDestroy(const hipblasLtHandle_t handle) {
+hipblasStatus_t hipblasLtDestroy(const hipblasLtHandle_t handle) {
     release_state((hipblasHandle_t)handle, true);
-    using Fn = hipblasStatus_t (*)(const hipblasLtHandle_t);
-    static Fn real = real_fn<Fn>("hipblasLtDestroy");
-    NativeScope ns_; return real ? real(handle) : HIPBLAS_STATUS_NOT_INITIALIZED;
+    OZ2_NATIVE(hipblasLtDestroy, HIPBLAS_STATUS_NOT_INITIALIZED, handle);
 }
-
-extern "C" hipblasStatus_t hipblasLtMatmul(hipblasLtHandle_t handle, hipblasLtMatmulDesc_t matmulDesc, const void* alpha, const void* A,
-                                           hipblasLtMatrixLayout_t Adesc, const void* B, hipblasLtMatrixLayout_t Bdesc, const void* beta,
-                                           const void* C, hipblasLtMatrixLayout_t Cdesc, void* D, hipblasLtMatrixLayout_t Ddesc,
-                                           const hipblasLtMatmulAlgo_t* algo, void* workspace, size_t workspaceSizeInBytes, hipStream_t stream) {
+hipblasStatus_t hipblasLtMatmul(hipblasLtHandle_t handle, hipblasLtMatmulDesc_t matmulDesc, const void* alpha, const void* A,
+                                hipblasLtMatrixLayout_t Adesc, const void* B, hipblasLtMatrixLayout_t Bdesc, const void* beta, const void* C,
+                                hipblasLtMatrixLayout_t Cdesc, void* D, hipblasLtMatrixLayout_t Ddesc, const hipblasLtMatmulAlgo_t* algo, void* workspace,
+                                size_t workspaceSizeInBytes, hipStream_t stream) {
     hipblasStatus_t st;
     if (lt_try(handle, matmulDesc, alpha, A, Adesc, B, Bdesc, beta, C, Cdesc, D, Ddesc, stream, &st)) return st;
-    using Fn = hipblasStatus_t (*)(hipblasLtHandle_t, hipblasLtMatmulDesc_t, const void*, const void*, hipblasLtMatrixLayout_t, const void*,
-                                   hipblasLtMatrixLayout_t, const void*, const void*, hipblasLtMatrixLayout_t, void*, hipblasLtMatrixLayout_t,
-                                   const hipblasLtMatmulAlgo_t*, void*, size_t, hipStream_t);
-    static Fn real = real_fn<Fn>("hipblasLtMatmul");
-    NativeScope ns_; return real ? real(handle, matmulDesc, alpha, A, Adesc, B, Bdesc, beta, C, Cdesc, D, Ddesc, algo, workspace, workspaceSizeInBytes, stream)
-                : HIPBLAS_STATUS_NOT_INITIALIZED;
+    OZ2_NATIVE(hipblasLtMatmul, HIPBLAS_STATUS_NOT_INITIALIZED, handle, matmulDesc, alpha, A, Adesc, B, Bdesc, beta, C, Cdesc, D, Ddesc, algo, workspace,
+               workspaceSizeInBytes, stream);
 }
+
+}  // extern "C"
 #pragma GCC visibility pop

@@ -1,6 +1,6 @@
 // Drives every entry point of the LD_PRELOAD hook (gemmul8_amd/csrc/oz2_hook.cpp, built with ASan + UBSan) against the mock
 // libraries of mock_gpu.cpp: growing shapes, stream switches, the skip-scaling cache, type switches, the ILP64 / Ex / batched /
-// hipblasLt forms, calls outside the emulator's range, the size floor, hipblasDestroy, and several host threads with their own handles.
+// hipblasLt / rocBLAS forms (the internal template by its mangled names), calls outside the emulator's range, the size floor, hipblasDestroy, and several host threads with their own handles.
 #include <hip/hip_runtime.h>
 #include <hipblas/hipblas.h>
 #include <hipblaslt/hipblaslt.h>
@@ -19,6 +19,32 @@ hipblasStatus_t mock_set_stream(hipblasHandle_t, hipStream_t);
 void* mock_lt_desc(int, int, unsigned);
 void* mock_lt_desc_bias(int, int, const void*, int);
 void mock_lt_free_desc(void*);
+// rocBLAS as oz2_hook.cpp interposes it: plain ints for rocblas_operation / rocblas_datatype / rocblas_status, void* for the handle
+int rocblas_destroy_handle(void*);
+int rocblas_gemm_ex(void*, int, int, int, int, int, const void*, const void*, int, int, const void*, int, int, const void*, const void*, int, int, void*, int,
+                    int, int, int, int32_t, uint32_t);
+#define ROCBLAS_DECL(LETTER, T, SYM32, SYM64)                                                                                              \
+    int rocblas_##LETTER##gemm(void*, int, int, int, int, int, const T*, const T*, int, const T*, int, const T*, T*, int);                 \
+    int rocblas_##LETTER##gemm_strided_batched(void*, int, int, int, int, int, const T*, const T*, int, long long, const T*, int, long long, const T*, T*, \
+                                               int, long long, int);                                                                      \
+    int rb_int_##LETTER##_32(void*, int, int, int, int, int, const T*, const T*, long, int, long, const T*, long, int, long, const T*, T*, long, int, long, \
+                             int) __asm__(SYM32);                                                                                         \
+    int rb_int_##LETTER##_64(void*, int, int, long, long, long, const T*, const T*, long, long, long, const T*, long, long, long, const T*, T*, long, long, \
+                             long, long) __asm__(SYM64);
+// rocblas_internal_gemm_template<T> / _64, called by their mangled names as rocSOLVER does
+ROCBLAS_DECL(s, float,
+             "_Z30rocblas_internal_gemm_templateIfE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_iiiPKT_S6_lilS6_lilS6_PS4_lili",
+             "_Z33rocblas_internal_gemm_template_64IfE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_lllPKT_S6_lllS6_lllS6_PS4_llll")
+ROCBLAS_DECL(d, double,
+             "_Z30rocblas_internal_gemm_templateIdE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_iiiPKT_S6_lilS6_lilS6_PS4_lili",
+             "_Z33rocblas_internal_gemm_template_64IdE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_lllPKT_S6_lllS6_lllS6_PS4_llll")
+ROCBLAS_DECL(c, hipComplex,
+             "_Z30rocblas_internal_gemm_templateI19rocblas_complex_numIfEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_iiiPKT_S8_lilS8_lilS8_PS6_lili",
+             "_Z33rocblas_internal_gemm_template_64I19rocblas_complex_numIfEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_lllPKT_S8_lllS8_lllS8_PS6_llll")
+ROCBLAS_DECL(z, hipDoubleComplex,
+             "_Z30rocblas_internal_gemm_templateI19rocblas_complex_numIdEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_iiiPKT_S8_lilS8_lilS8_PS6_lili",
+             "_Z33rocblas_internal_gemm_template_64I19rocblas_complex_numIdEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_lllPKT_S8_lllS8_lllS8_PS6_llll")
+#undef ROCBLAS_DECL
 }
 #define CHECK(x)                                                       \
     do {                                                               \
@@ -142,7 +168,90 @@ batch_done:
     CHECK(hipblasDestroy(h) == HIPBLAS_STATUS_SUCCESS);  // frees the handle's three buffers first
 }
 
+// Every exported GEMM entry point once where the environment selects its type (emulated: the emulation's counter rises, the native one
+// does not) and once where it does not -- the type's GEMMUL8_NUM_MOD_* unset, or GEMMUL8_HOOK_ROCBLAS unset for the rocBLAS names -- where
+// exactly one native call is made.  Single-threaded: it switches the environment between calls.
+template <typename F> static void emulated_then_native(F call, bool rocblas) {
+    const char* const nmod[4][2] = {{"GEMMUL8_NUM_MOD_S", "8"}, {"GEMMUL8_NUM_MOD_D", "15"}, {"GEMMUL8_NUM_MOD_C", "8"}, {"GEMMUL8_NUM_MOD_Z", "15"}};
+    for (auto& v : nmod) setenv(v[0], v[1], 1);
+    if (rocblas) setenv("GEMMUL8_HOOK_ROCBLAS", "1", 1);
+    long emu = mock_emulated_calls(), nat = mock_native_calls();
+    CHECK(call() == 0);  // HIPBLAS_STATUS_SUCCESS == rocblas_status_success == 0
+    CHECK(mock_emulated_calls() > emu);
+    CHECK(mock_native_calls() == nat);
+    if (rocblas) unsetenv("GEMMUL8_HOOK_ROCBLAS");
+    else
+        for (auto& v : nmod) unsetenv(v[0]);
+    emu = mock_emulated_calls(), nat = mock_native_calls();
+    CHECK(call() == 0);
+    CHECK(mock_emulated_calls() == emu);
+    CHECK(mock_native_calls() == nat + 1);
+    for (auto& v : nmod) unsetenv(v[0]);
+}
+template <typename T, typename Gemm, typename Gemm64, typename Sb, typename RGemm, typename RSb, typename RInt32, typename RInt64>
+static void every_typed_entry_point(hipblasHandle_t h, hipDataType type, hipblasComputeType_t compute, int rocblas_type, Gemm gemm, Gemm64 gemm_64, Sb sb,
+                                    RGemm rgemm, RSb rsb, RInt32 rint32, RInt64 rint64) {
+    const int m = 40, n = 30, k = 20, batch = 3;
+    const long long sa = m * k, sb_ = k * n, sc = m * n;
+    std::vector<T> A(sa * batch), B(sb_ * batch), C(sc * batch);
+    const T one{1}, zero{0};
+    const hipblasOperation_t N = HIPBLAS_OP_N;
+    emulated_then_native([&] { return (int)gemm(h, N, N, m, n, k, &one, A.data(), m, B.data(), k, &zero, C.data(), m); }, false);
+    emulated_then_native([&] { return (int)gemm_64(h, N, N, m, n, k, &one, A.data(), m, B.data(), k, &zero, C.data(), m); }, false);
+    emulated_then_native([&] { return (int)hipblasGemmEx(h, N, N, m, n, k, &one, A.data(), type, m, B.data(), type, k, &zero, C.data(), type, m, compute, HIPBLAS_GEMM_DEFAULT); }, false);
+    emulated_then_native([&] { return (int)hipblasGemmEx_64(h, N, N, m, n, k, &one, A.data(), type, m, B.data(), type, k, &zero, C.data(), type, m, compute, HIPBLAS_GEMM_DEFAULT); }, false);
+    emulated_then_native([&] { return (int)hipblasGemmExWithFlags(h, N, N, m, n, k, &one, A.data(), type, m, B.data(), type, k, &zero, C.data(), type, m, compute, HIPBLAS_GEMM_DEFAULT, HIPBLAS_GEMM_FLAGS_NONE); }, false);
+    emulated_then_native([&] { return (int)hipblasGemmExWithFlags_64(h, N, N, m, n, k, &one, A.data(), type, m, B.data(), type, k, &zero, C.data(), type, m, compute, HIPBLAS_GEMM_DEFAULT, HIPBLAS_GEMM_FLAGS_NONE); }, false);
+    emulated_then_native([&] { return (int)sb(h, N, N, m, n, k, &one, A.data(), m, sa, B.data(), k, sb_, &zero, C.data(), m, sc, batch); }, false);
+    emulated_then_native([&] { return (int)hipblasGemmStridedBatchedEx(h, N, N, m, n, k, &one, A.data(), type, m, sa, B.data(), type, k, sb_, &zero, C.data(), type, m, sc, batch, compute, HIPBLAS_GEMM_DEFAULT); }, false);
+    // rocBLAS: 111 = rocblas_operation_none; the handle of a hipBLAS call is the rocBLAS handle
+    emulated_then_native([&] { return rgemm(h, 111, 111, m, n, k, &one, A.data(), m, B.data(), k, &zero, C.data(), m); }, true);
+    emulated_then_native([&] { return rsb(h, 111, 111, m, n, k, &one, A.data(), m, sa, B.data(), k, sb_, &zero, C.data(), m, sc, batch); }, true);
+    emulated_then_native([&] { return rocblas_gemm_ex(h, 111, 111, m, n, k, &one, A.data(), rocblas_type, m, B.data(), rocblas_type, k, &zero, C.data(), rocblas_type, m, C.data(), rocblas_type, m, rocblas_type, 0, 0, 0); }, true);
+    emulated_then_native([&] { return rint32(h, 111, 111, m, n, k, &one, A.data(), 0, m, sa, B.data(), 0, k, sb_, &zero, C.data(), 0, m, sc, 1); }, true);  // one item
+    emulated_then_native([&] { return rint64(h, 111, 111, m, n, k, &one, A.data(), 0, m, sa, B.data(), 0, k, sb_, &zero, C.data(), 0, m, sc, batch); }, true);  // strided batch
+}
+static void every_entry_point() {
+    hipblasHandle_t h;
+    mock_create(&h);
+    every_typed_entry_point<float>(h, HIP_R_32F, HIPBLAS_COMPUTE_32F, 151, hipblasSgemm, hipblasSgemm_64, hipblasSgemmStridedBatched, rocblas_sgemm,
+                                   rocblas_sgemm_strided_batched, rb_int_s_32, rb_int_s_64);
+    every_typed_entry_point<double>(h, HIP_R_64F, HIPBLAS_COMPUTE_64F, 152, hipblasDgemm, hipblasDgemm_64, hipblasDgemmStridedBatched, rocblas_dgemm,
+                                    rocblas_dgemm_strided_batched, rb_int_d_32, rb_int_d_64);
+    every_typed_entry_point<hipComplex>(h, HIP_C_32F, HIPBLAS_COMPUTE_32F, 154, hipblasCgemm, hipblasCgemm_64, hipblasCgemmStridedBatched, rocblas_cgemm,
+                                        rocblas_cgemm_strided_batched, rb_int_c_32, rb_int_c_64);
+    every_typed_entry_point<hipDoubleComplex>(h, HIP_C_64F, HIPBLAS_COMPUTE_64F, 155, hipblasZgemm, hipblasZgemm_64, hipblasZgemmStridedBatched, rocblas_zgemm,
+                                              rocblas_zgemm_strided_batched, rb_int_z_32, rb_int_z_64);
+    setenv("GEMMUL8_NUM_MOD_D", "15", 1);
+    const double one = 1, zero = 0;
+    std::vector<double> A(40 * 20 * 3), B(20 * 30 * 3), C(40 * 30 * 3);
+    const hipblasOperation_t N = HIPBLAS_OP_N;
+    // an ILP64 form with a dimension an int cannot hold: native (the stand-in reads no operand)
+    long nat = mock_native_calls(), emu = mock_emulated_calls();
+    CHECK(hipblasDgemm_64(h, N, N, 40, 30, 20, &one, A.data(), (int64_t)2147483647 + 41, B.data(), 20, &zero, C.data(), 40) == HIPBLAS_STATUS_SUCCESS);
+    CHECK(mock_native_calls() == nat + 1 && mock_emulated_calls() == emu);
+    // the ILP64 forms keep the plain forms' early outs
+    CHECK(hipblasDgemm_64(h, N, N, 40, 0, 20, &one, A.data(), 40, B.data(), 20, &zero, C.data(), 40) == HIPBLAS_STATUS_SUCCESS);
+    CHECK(hipblasGemmExWithFlags_64(h, N, N, 40, 30, 20, &one, A.data(), HIP_R_64F, 40, nullptr, HIP_R_64F, 20, &zero, C.data(), HIP_R_64F, 40, HIPBLAS_COMPUTE_64F,
+                                    HIPBLAS_GEMM_DEFAULT, HIPBLAS_GEMM_FLAGS_NONE) == HIPBLAS_STATUS_INVALID_VALUE);
+    CHECK(mock_native_calls() == nat + 1 && mock_emulated_calls() == emu);
+    // the strided-batched forms do NOT early-out: an empty batch is the native routine's to answer
+    CHECK(hipblasDgemmStridedBatched(h, N, N, 40, 30, 20, &one, A.data(), 40, 800, B.data(), 20, 600, &zero, C.data(), 40, 1200, 0) == HIPBLAS_STATUS_SUCCESS);
+    CHECK(mock_native_calls() == nat + 2 && mock_emulated_calls() == emu);
+    CHECK(hipblasGemmStridedBatchedEx(h, N, N, 40, 30, 20, &one, A.data(), HIP_R_64F, 40, 800, B.data(), HIP_R_64F, 20, 600, &zero, C.data(), HIP_R_64F, 40, 1200, 0,
+                                      HIPBLAS_COMPUTE_64F, HIPBLAS_GEMM_DEFAULT) == HIPBLAS_STATUS_SUCCESS);
+    CHECK(mock_native_calls() == nat + 3 && mock_emulated_calls() == emu);
+    // rocblas_gemm_ex serves only the in-place form: c != d is rocBLAS's
+    setenv("GEMMUL8_HOOK_ROCBLAS", "1", 1);
+    CHECK(rocblas_gemm_ex(h, 111, 111, 40, 30, 20, &one, A.data(), 152, 40, B.data(), 152, 20, &zero, C.data(), 152, 40, C.data() + 1200, 152, 40, 152, 0, 0, 0) == 0);
+    CHECK(mock_native_calls() == nat + 4 && mock_emulated_calls() == emu);
+    unsetenv("GEMMUL8_HOOK_ROCBLAS");
+    CHECK(rocblas_destroy_handle(h) == 0);  // releases the state the rocBLAS calls left under this handle, then the handle
+    setenv("GEMMUL8_NUM_MOD_S", "8", 1);
+}
+
 int main() {
+    setenv("GEMMUL8_HOOK_STATS", "1", 1);  // the line printed at exit counts every call above and below
     setenv("GEMMUL8_NUM_MOD_D", "15", 1);
     setenv("GEMMUL8_NUM_MOD_S", "8", 1);
     setenv("GEMMUL8_SKIP_SCALE_A", "1", 1);
@@ -152,6 +261,7 @@ int main() {
     setenv("GEMMUL8_MAX_K", "512", 1);
     setenv("GEMMUL8_MAX_NUM_MOD", "15", 1);
     one_thread(0);
+    every_entry_point();
     std::vector<std::thread> ts;
     for (int i = 1; i <= 4; ++i) ts.emplace_back(one_thread, i);
     for (auto& t : ts) t.join();

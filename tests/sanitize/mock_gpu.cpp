@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE for tests/test_sanitizers.py: a host-memory stand-in for what oz2_hook.cpp calls -- the HIP runtime subset it
-// uses, the "real" hipBLAS / hipBLASLt routines it forwards to (found through dlsym(RTLD_NEXT)), and the libgemmul8 C ABI -- so that
+// uses, the "real" hipBLAS / hipBLASLt / rocBLAS routines it forwards to (found through dlsym(RTLD_NEXT)), and the libgemmul8 C ABI -- so that
 // the hook's host logic (per-handle state, grow-only stream-ordered buffers, skip-scaling cache, stream switches, plan cache,
 // descriptor decoding) can run under AddressSanitizer / UBSan on a machine without a GPU.  gemmul8_gemm here WRITES every byte of
 // the three workspaces at the size gemmul8_work_size reports, so an under-sized or freed buffer is a sanitizer error.
@@ -59,16 +59,85 @@ NATIVE_GEMM(hipblasSgemm, float, int)
 NATIVE_GEMM(hipblasDgemm, double, int)
 NATIVE_GEMM(hipblasCgemm, hipComplex, int)
 NATIVE_GEMM(hipblasZgemm, hipDoubleComplex, int)
+NATIVE_GEMM(hipblasSgemm_64, float, int64_t)
 NATIVE_GEMM(hipblasDgemm_64, double, int64_t)
-EXPORT hipblasStatus_t hipblasGemmEx(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const void*, const void*, hipDataType, int,
-                                     const void*, hipDataType, int, const void*, void*, hipDataType, int, hipblasComputeType_t, hipblasGemmAlgo_t) {
+NATIVE_GEMM(hipblasCgemm_64, hipComplex, int64_t)
+NATIVE_GEMM(hipblasZgemm_64, hipDoubleComplex, int64_t)
+// the remaining natives only count: the driver checks where a call went, not what the stand-in wrote
+#define NATIVE_GEMM_EX(NAME, I, ...)                                                                                                   \
+    EXPORT hipblasStatus_t NAME(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, I, I, I, const void*, const void*, hipDataType, I, \
+                                const void*, hipDataType, I, const void*, void*, hipDataType, I, hipblasComputeType_t, hipblasGemmAlgo_t   \
+                                __VA_OPT__(, ) __VA_ARGS__) {                                                                          \
+        ++g_native_calls;                                                                                                              \
+        return HIPBLAS_STATUS_SUCCESS;                                                                                                 \
+    }
+NATIVE_GEMM_EX(hipblasGemmEx, int)
+NATIVE_GEMM_EX(hipblasGemmEx_64, int64_t)
+NATIVE_GEMM_EX(hipblasGemmExWithFlags, int, hipblasGemmFlags_t)
+NATIVE_GEMM_EX(hipblasGemmExWithFlags_64, int64_t, hipblasGemmFlags_t)
+#define NATIVE_SB(NAME, T)                                                                                                             \
+    EXPORT hipblasStatus_t NAME(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const T*, const T*, int, long long, \
+                                const T*, int, long long, const T*, T*, int, long long, int) {                                         \
+        ++g_native_calls;                                                                                                              \
+        return HIPBLAS_STATUS_SUCCESS;                                                                                                 \
+    }
+NATIVE_SB(hipblasSgemmStridedBatched, float)
+NATIVE_SB(hipblasDgemmStridedBatched, double)
+NATIVE_SB(hipblasCgemmStridedBatched, hipComplex)
+NATIVE_SB(hipblasZgemmStridedBatched, hipDoubleComplex)
+EXPORT hipblasStatus_t hipblasGemmStridedBatchedEx(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const void*, const void*,
+                                                   hipDataType, int, hipblasStride, const void*, hipDataType, int, hipblasStride, const void*, void*,
+                                                   hipDataType, int, hipblasStride, int, hipblasComputeType_t, hipblasGemmAlgo_t) {
     ++g_native_calls;
     return HIPBLAS_STATUS_SUCCESS;
 }
-EXPORT hipblasStatus_t hipblasDgemmStridedBatched(hipblasHandle_t, hipblasOperation_t, hipblasOperation_t, int, int, int, const double*, const double*, int,
-                                                  long long, const double*, int, long long, const double*, double*, int, long long, int) {
+
+// ---- "real" rocBLAS, with the plain-int signatures oz2_hook.cpp interposes: a rocBLAS handle is the hipBLAS handle (a MockHandle)
+EXPORT int rocblas_get_stream(void* h, hipStream_t* s) { *s = ((MockHandle*)h)->stream; return 0; }
+EXPORT int rocblas_destroy_handle(void* h) { delete (MockHandle*)h; return 0; }
+EXPORT int rocblas_get_version_string_size(size_t* n) { *n = sizeof "5.2.0.mock"; return 0; }
+EXPORT int rocblas_get_version_string(char* buf, size_t n) { std::memcpy(buf, "5.2.0.mock", n < sizeof "5.2.0.mock" ? n : sizeof "5.2.0.mock"); return 0; }
+#define NATIVE_ROCBLAS(LETTER, T, SYM32, SYM64)                                                                                        \
+    EXPORT int rocblas_##LETTER##gemm(void*, int, int, int, int, int, const T*, const T*, int, const T*, int, const T*, T*, int) {     \
+        ++g_native_calls;                                                                                                              \
+        return 0;                                                                                                                      \
+    }                                                                                                                                  \
+    EXPORT int rocblas_##LETTER##gemm_strided_batched(void*, int, int, int, int, int, const T*, const T*, int, long long, const T*, int, long long, \
+                                                      const T*, T*, int, long long, int) {                                            \
+        ++g_native_calls;                                                                                                              \
+        return 0;                                                                                                                      \
+    }                                                                                                                                  \
+    EXPORT int mock_rb_int_##LETTER##_32(void*, int, int, int, int, int, const T*, const T*, long, int, long, const T*, long, int, long, const T*, T*, \
+                                         long, int, long, int) __asm__(SYM32);                                                         \
+    int mock_rb_int_##LETTER##_32(void*, int, int, int, int, int, const T*, const T*, long, int, long, const T*, long, int, long, const T*, T*, long, \
+                                  int, long, int) {                                                                                    \
+        ++g_native_calls;                                                                                                              \
+        return 0;                                                                                                                      \
+    }                                                                                                                                  \
+    EXPORT int mock_rb_int_##LETTER##_64(void*, int, int, long, long, long, const T*, const T*, long, long, long, const T*, long, long, long, const T*, \
+                                         T*, long, long, long, long) __asm__(SYM64);                                                   \
+    int mock_rb_int_##LETTER##_64(void*, int, int, long, long, long, const T*, const T*, long, long, long, const T*, long, long, long, const T*, T*,  \
+                                  long, long, long, long) {                                                                            \
+        ++g_native_calls;                                                                                                              \
+        return 0;                                                                                                                      \
+    }
+// rocblas_internal_gemm_template<T> / _64 under the mangled names rocSOLVER binds to (rocBLAS 5.x)
+NATIVE_ROCBLAS(s, float,
+               "_Z30rocblas_internal_gemm_templateIfE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_iiiPKT_S6_lilS6_lilS6_PS4_lili",
+               "_Z33rocblas_internal_gemm_template_64IfE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_lllPKT_S6_lllS6_lllS6_PS4_llll")
+NATIVE_ROCBLAS(d, double,
+               "_Z30rocblas_internal_gemm_templateIdE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_iiiPKT_S6_lilS6_lilS6_PS4_lili",
+               "_Z33rocblas_internal_gemm_template_64IdE15rocblas_status_P15_rocblas_handle18rocblas_operation_S3_lllPKT_S6_lllS6_lllS6_PS4_llll")
+NATIVE_ROCBLAS(c, hipComplex,
+               "_Z30rocblas_internal_gemm_templateI19rocblas_complex_numIfEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_iiiPKT_S8_lilS8_lilS8_PS6_lili",
+               "_Z33rocblas_internal_gemm_template_64I19rocblas_complex_numIfEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_lllPKT_S8_lllS8_lllS8_PS6_llll")
+NATIVE_ROCBLAS(z, hipDoubleComplex,
+               "_Z30rocblas_internal_gemm_templateI19rocblas_complex_numIdEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_iiiPKT_S8_lilS8_lilS8_PS6_lili",
+               "_Z33rocblas_internal_gemm_template_64I19rocblas_complex_numIdEE15rocblas_status_P15_rocblas_handle18rocblas_operation_S5_lllPKT_S8_lllS8_lllS8_PS6_llll")
+EXPORT int rocblas_gemm_ex(void*, int, int, int, int, int, const void*, const void*, int, int, const void*, int, int, const void*, const void*, int, int,
+                           void*, int, int, int, int, int32_t, uint32_t) {
     ++g_native_calls;
-    return HIPBLAS_STATUS_SUCCESS;
+    return 0;
 }
 
 // ---- "real" hipBLASLt: descriptors are plain structs
