@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libgemmul8.so")
 S, D, Cx, Z = 0, 1, 2, 3
 INT8, FP8 = 0, 1
 OPS = {"N": 0, "T": 1, "C": 2}
+UPLO = {"L": 0, "U": 1}
 
 
 class Layout(C.Structure):
@@ -35,7 +36,7 @@ _lib = None
 
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
            "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
-           "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes"]
+           "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
 
@@ -118,6 +119,9 @@ def bind(L):
     L.gemmul8_gemm_batched.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_longlong, C.c_void_p, C.c_size_t, C.c_longlong, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_longlong, C.c_size_t, C.c_uint, C.c_int, C.c_void_p]
+    L.gemmul8_syrk.restype = C.c_int
+    L.gemmul8_syrk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
     L.gemmul8_set_fp8_bound_mode.restype = C.c_int
     L.gemmul8_set_fp8_bound_mode.argtypes = [C.c_int]
     L.gemmul8_set_nonfinite_mode.restype = C.c_int
@@ -192,6 +196,36 @@ def gemm(A, B, num_moduli, fastmode=False, backend=INT8, opA="N", opB="N", alpha
                             B.data_ptr(), ldb, be.ctypes.data, C_out.data_ptr(), C_out.shape[1], num_moduli, int(fastmode),
                             work.data_ptr(), None, None, 0, 0, 0, 0, tm)
     check(rc, "gemmul8_gemm")
+    return C_out, (list(tm) if timers else None), work
+
+
+def syrk(A, num_moduli, uplo="L", trans="N", fastmode=False, alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, timers=False):
+    """One triangle of C = alpha*A*A^T + beta*C (trans "N", A is n x k) or alpha*A^T*A + beta*C (trans "T", A is k x n; plain transpose
+    for complex types too) through gemmul8_syrk: INT8 backend, the triangle `uplo` ("L" / "U", diagonal included) bit-identical to
+    `gemm(A, A, opA=trans, opB="T" if trans == "N" else "N")`, the other strict triangle of C_out neither read nor written.
+    A and C_out are column-major matrices held as tensors of shape (cols, rows), as in `gemm`; a fresh C_out is zero-filled.
+    Returns (C, timers_ns or None, work)."""
+    import numpy as np
+    import torch
+    assert A.is_cuda and A.is_contiguous()
+    dt = A.dtype
+    if C_out is not None and (C_out.dtype != dt or not C_out.is_contiguous()):
+        raise TypeError("A and C_out must share one dtype and be contiguous")
+    lda = A.shape[1]
+    n, k = (lda, A.shape[0]) if trans == "N" else (A.shape[0], lda)
+    if C_out is None:
+        C_out = torch.zeros((n, n), dtype=dt, device=A.device)
+    if work is None:
+        tot, _, _ = work_size(dt.is_complex, INT8, n, n, k, num_moduli)
+        work = torch.empty(tot, dtype=torch.uint8, device=A.device)
+    np_dt = {torch.float32: np.float32, torch.float64: np.float64, torch.complex64: np.complex64, torch.complex128: np.complex128}[dt]
+    al = np.array([alpha], dtype=np_dt)
+    be = np.array([beta], dtype=np_dt)
+    tm = (C.c_double * 4)() if timers else None
+    st = stream if stream is not None else torch.cuda.current_stream(A.device).cuda_stream
+    rc = lib().gemmul8_syrk(st, _dtype_code(dt), INT8, UPLO[uplo], OPS[trans], n, k, al.ctypes.data, A.data_ptr(), lda, be.ctypes.data,
+                            C_out.data_ptr(), C_out.shape[1], num_moduli, int(fastmode), work.data_ptr(), tm)
+    check(rc, "gemmul8_syrk")
     return C_out, (list(tm) if timers else None), work
 
 

@@ -103,7 +103,8 @@ __device__ __forceinline__ void crt_load(const CrtArgs& a, const CrtPos& p, size
         }
 }
 
-template <typename U, bool CPLX, typename MID, int LB, bool LDS_STORE, int NMAX>
+// TRI (crt_tri_kernel): only the entries of the triangle a.tri names are read and stored -- a unit that the diagonal cuts moves element by element
+template <typename U, bool CPLX, typename MID, int LB, bool LDS_STORE, int NMAX, bool TRI = false>
 __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size_t gid, size_t total, unsigned row_groups,
                                          const typename CrtVec<MID, LB, (CPLX ? 2 : 1)>::Vec (&c)[NMAX], char* stage) {
     constexpr int COMPS = CPLX ? 2 : 1;
@@ -129,7 +130,8 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
     const int16_t* sftA_z = (const int16_t*)((const char*)a.sftA + zw);
     const int sB = (int)((const int16_t*)((const char*)a.sftB + zw))[col];
     U* Cc = (U*)((char*)a.C + blockIdx.z * a.bc) + (col * a.ldc) * COMPS;
-    const bool full = i0 + ROWS <= a.m;  // all ROWS rows exist: the old and new C values move as one vector per thread
+    auto stored = [&](size_t row) { return row < a.m && (!TRI || (a.tri == 1 ? row >= col : row <= col)); };
+    const bool full = i0 + ROWS <= a.m && (!TRI || (a.tri == 1 ? i0 >= col : i0 + ROWS - 1 <= col));  // all ROWS rows exist (and are stored): the old and new C values move as one vector per thread
     const bool beta0 = be[0] == (U)0 && (!CPLX || be[1] == (U)0);
     const bool reads_c = (mode == 0 && !beta0) || mode == 2 || mode == 4;
     U outv[NV];
@@ -172,7 +174,7 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
             } else {
 #pragma unroll
                 for (int e = p0; e < p0 + PASS; ++e)
-                    if (i0 + e / COMPS < a.m) oldc[e] = Cc[i0 * COMPS + e];
+                    if (stored(i0 + e / COMPS)) oldc[e] = Cc[i0 * COMPS + e];
             }
         }
 #pragma unroll
@@ -215,7 +217,8 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
         const size_t colf = first / row_groups;
         const size_t i0f = (first - colf * row_groups) * ROWS;
         char* wdst = (char*)((U*)((char*)a.C + blockIdx.z * a.bc) + (colf * a.ldc + i0f) * COMPS);
-        const bool wave_fast = last < total && last / row_groups == colf && i0f + (size_t)64 * ROWS <= a.m && ((uintptr_t)wdst & 15u) == 0;
+        const bool wave_fast = last < total && last / row_groups == colf && i0f + (size_t)64 * ROWS <= a.m && ((uintptr_t)wdst & 15u) == 0 &&
+                               (!TRI || (a.tri == 1 ? i0f >= colf : i0f + (size_t)64 * ROWS - 1 <= colf));
         if (wave_fast) {
             crt_wave_store<J>(stage + (size_t)(threadIdx.x >> 6) * 64 * OUTB, outv, wdst, lane);
             return;
@@ -232,7 +235,7 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
     } else {
 #pragma unroll
         for (int e = 0; e < NV; ++e)
-            if (i0 + e / COMPS < a.m) Cc[i0 * COMPS + e] = outv[e];
+            if (stored(i0 + e / COMPS)) Cc[i0 * COMPS + e] = outv[e];
     }
 }
 
@@ -272,6 +275,25 @@ __global__ void __launch_bounds__(OZ2_CRT_BLOCK) __attribute__((amdgpu_waves_per
     }
 }
 
+// One triangle of a square C (gemmul8_syrk): crt_kernel's units, loads and arithmetic -- a unit wholly outside the triangle leaves before it
+// loads a residue (the residue tiles there were never computed), one the diagonal cuts stores element by element.
+template <typename U, bool CPLX, int NMAX>
+__global__ void __launch_bounds__(OZ2_CRT_BLOCK) __attribute__((amdgpu_waves_per_eu(OZ2_CRT_WAVES, 8))) crt_tri_kernel(const CrtArgs a) {
+    constexpr int COMPS = CPLX ? 2 : 1, LB = OZ2_CRT_LB;
+    constexpr int ROWS = LB / COMPS;
+    constexpr int OUTB = ROWS * COMPS * (int)sizeof(U);
+    static_assert(OUTB % 16 == 0, "a thread's results are whole 16-byte pieces");
+    constexpr bool LDS_STORE = OUTB > 16;
+    __shared__ __attribute__((aligned(16))) char stage[LDS_STORE ? OZ2_CRT_BLOCK * OUTB : 16];
+    const unsigned row_groups = (unsigned)((a.m + ROWS - 1) / ROWS);
+    const size_t total = (size_t)row_groups * a.n;
+    const size_t gid = (size_t)blockIdx.x * OZ2_CRT_BLOCK + threadIdx.x;
+    const CrtPos pos = crt_pos<ROWS>(gid, total, row_groups);
+    if (a.tri == 1 ? pos.i0 + ROWS - 1 < pos.col : pos.i0 > pos.col) return;  // (a wave that takes crt_wave_store lies wholly inside: none of its lanes leaves here)
+    typename CrtVec<int8_t, LB, COMPS>::Vec cb[NMAX];
+    crt_load<int8_t, LB, COMPS, NMAX>(a, pos, gid, cb);
+    crt_unit<U, CPLX, int8_t, LB, LDS_STORE, NMAX, true>(a, pos, gid, total, row_groups, cb, stage);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // LDS-DMA form of the CRT kernel for INT8 residues (round 3).  One wave per workgroup; a unit = 1024 consecutive bytes of one column
@@ -706,6 +728,42 @@ hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, si
         }
     }
 #undef OZ2_CRT
+    return hipGetLastError();
+}
+
+hipError_t launch_crt_tri(hipStream_t stream, int dtype, unsigned N, size_t n, int tri, const void* Cmid, size_t ld_mid, size_t plane_stride,
+                          const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc) {
+    if (n == 0) return hipSuccess;
+    if (tri != 1 && tri != 2) return hipErrorInvalidValue;
+    CrtArgs a{};
+    a.Cmid = Cmid;
+    a.ld_mid = ld_mid;
+    a.plane_stride = plane_stride;
+    a.m = n;
+    a.n = n;
+    a.sftA = sftA;
+    a.sftB = sftB;
+    a.C = C;
+    a.ldc = ldc;
+    a.tri = tri;
+    fill_crt_tables(a, dtype, kINT8, N);
+    fill_crt_scalars(a, dtype, alpha, beta, scalars_on_device);
+    const size_t rows_per_thread = OZ2_CRT_LB / (is_complex(dtype) ? 2 : 1);
+    const size_t threads = ((n + rows_per_thread - 1) / rows_per_thread) * n;
+    dim3 grid((unsigned)((threads + OZ2_CRT_BLOCK - 1) / OZ2_CRT_BLOCK));
+#define OZ2_CRT_TRI(U, CP)                                                                                          \
+    do {                                                                                                            \
+        if (N > 14) hipLaunchKernelGGL((crt_tri_kernel<U, CP, 20>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);        \
+        else hipLaunchKernelGGL((crt_tri_kernel<U, CP, 14>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);               \
+    } while (0)
+    switch (dtype) {
+    case kF32: OZ2_CRT_TRI(float, false); break;
+    case kF64: OZ2_CRT_TRI(double, false); break;
+    case kC32: OZ2_CRT_TRI(float, true); break;
+    case kC64: OZ2_CRT_TRI(double, true); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef OZ2_CRT_TRI
     return hipGetLastError();
 }
 

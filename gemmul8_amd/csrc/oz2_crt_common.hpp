@@ -24,6 +24,7 @@ struct CrtArgs {
     double Phi, Plo, invP;
     double q1[20], qh[20], ql[20];
     size_t bw, bc;  // batched launch (crt_kernel, gridDim.z items): bytes between the items' workspaces / between their C matrices
+    int tri;        // crt_tri_kernel: 1 = only entries i >= j, 2 = only i <= j
 };
 
 // host side (oz2_crt.hip)

@@ -645,6 +645,75 @@ int gemmul8_gemm(void* stream_, int dtype, int backend, int op_A, int op_B, size
     return GEMMUL8_OK;
 }
 
+// ---- symmetric rank-k update (no counterpart in the reference).  op(A) op(A)^T is the GEMM (trans, trans == N ? T : N) of A with itself: both
+// operands then take the same kernel form through every scaling kernel (row-strided for trans = N, K-major for T), the bound product
+// |A| |A|^T is a symmetric integer matrix (rowmax == colmax), and residue and bound planes have one format for both sides -- so B's planes and
+// shifts ARE A's (tests/test_syrk_premise.py pins this on the oracle).  One operand pass (skipB), the residue GEMMs over the tiles of one
+// triangle, the CRT over its entries.  The accurate mode's bound GEMM stays the full square.
+int gemmul8_syrk(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda,
+                 const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (timers_ns) timers_ns[0] = timers_ns[1] = timers_ns[2] = timers_ns[3] = 0.0;
+    if (dtype < 0 || dtype > 3 || backend < 0 || backend > 1) return GEMMUL8_E_ARG;
+    if (uplo == 122) uplo = GEMMUL8_LOWER;  // hipblasFillMode_t
+    else if (uplo == 121) uplo = GEMMUL8_UPPER;
+    trans = norm_op(trans);
+    if ((uplo != GEMMUL8_LOWER && uplo != GEMMUL8_UPPER) || (trans != 0 && trans != 1)) return GEMMUL8_E_ARG;
+    if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
+    if (!alpha || !beta || !A || !C || !work) return GEMMUL8_E_ARG;
+    if (k > (size_t(1) << 17)) return GEMMUL8_E_ARG;
+    if (backend == kFP8) return GEMMUL8_E_UNSUPPORTED;  // the FP6 panel images of A and B differ in layout: B's planes are not A's
+    if (n == 0 || k == 0) return GEMMUL8_OK;
+    const bool cplx = is_complex(dtype);
+    gemmul8_layout L;
+    int rc = gemmul8_get_layout(dtype, backend, n, n, k, N, work, nullptr, nullptr, 0, 0, &L);
+    if (rc) return rc;
+    L.B_lo = L.A_lo, L.B_bound = L.A_bound, L.sftB = L.sftA, L.sizeB = L.sizeA, L.part_strideB = L.part_strideA;
+    Timer* T = timers_ns ? thread_timer() : nullptr;
+    if (T && hipEventRecord(T->ev[0], stream) != hipSuccess) {
+        (void)hipGetLastError();
+        T = nullptr;
+    }
+    const int op_A = trans, op_B = trans == 0 ? 1 : 0;
+    rc = scale_nf(stream, dtype, backend, op_A, op_B, n, n, k, A, lda, A, lda, N, fastmode, 0, N, &L, 0, 1, false);
+    if (rc) return rc;
+    if (T) OZ2_HIP(hipEventRecord(T->ev[1], stream));
+    const int tri = uplo == GEMMUL8_LOWER ? 1 : 2;
+    const int8_t* A_lo = (const int8_t*)L.A_lo;
+    if (!cplx) {
+        OZ2_HIP(launch_gemm_i8_mod(stream, A_lo, A_lo, L.sizeA, L.sizeA, L.kp, n, n, 0, (int)N, (int8_t*)L.C_mid, L.mp, L.sizeC, true, tri));
+    } else {  // X = ArAr^T, Y = AiAi^T, Z = (Ar+Ai)(Ar+Ai)^T as in gemmul8_lowprec_gemm, each over the triangle's tiles
+        const size_t per_mod = 2 * L.sizeC;
+        size_t chunk = L.scratch_bytes / per_mod;
+        if (chunk == 0) return GEMMUL8_E_ARG;
+        if (const size_t want = (size_t)knobs().cplx_chunk; want >= 1 && want < chunk) chunk = want;
+        int8_t* rx = (int8_t*)L.scratch;
+        for (unsigned t0 = 0; t0 < N; t0 += (unsigned)chunk) {
+            const unsigned t1 = std::min<unsigned>(N, t0 + (unsigned)chunk);
+            int8_t* ry = rx + (size_t)(t1 - t0) * L.sizeC;
+            const int8_t *Ar = A_lo + (size_t)t0 * L.sizeA, *Ai = Ar + L.part_strideA, *As = Ar + 2 * L.part_strideA;
+            OZ2_HIP(launch_gemm_i8_mod(stream, Ar, Ar, L.sizeA, L.sizeA, L.kp, n, n, (int)t0, (int)t1, rx, L.mp, L.sizeC, false, tri));
+            OZ2_HIP(launch_gemm_i8_mod(stream, Ai, Ai, L.sizeA, L.sizeA, L.kp, n, n, (int)t0, (int)t1, ry, L.mp, L.sizeC, false, tri));
+            OZ2_HIP(launch_gemm_i8_cplx(stream, As, As, L.sizeA, L.sizeA, L.kp, n, n, (int)t0, (int)t1, rx, ry, L.sizeC,
+                                        (int8_t*)L.C_mid + (size_t)t0 * 2 * L.sizeC, L.mp, 2 * L.sizeC, tri));
+        }
+    }
+    if (T) OZ2_HIP(hipEventRecord(T->ev[2], stream));
+    OZ2_HIP(launch_crt_tri(stream, dtype, N, n, tri, L.C_mid, L.mp, L.sizeC, L.sftA, L.sftA, alpha, beta, scalars_on_device(alpha), C, ldc));
+    if (T) {
+        OZ2_HIP(hipEventRecord(T->ev[3], stream));
+        OZ2_HIP(hipEventSynchronize(T->ev[3]));
+        float ms;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[0], T->ev[1]));
+        timers_ns[0] = ms * 1e6;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[1], T->ev[2]));
+        timers_ns[1] = ms * 1e6;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[2], T->ev[3]));
+        timers_ns[3] = ms * 1e6;
+    }
+    return GEMMUL8_OK;
+}
+
 int gemmul8_add_f64(void* stream_, double* dst, const double* src, size_t count) {
     if (!dst || !src || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15)) return GEMMUL8_E_ARG;
     OZ2_HIP(launch_add_f64((hipStream_t)stream_, dst, src, count));

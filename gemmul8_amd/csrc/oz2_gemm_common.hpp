@@ -87,6 +87,12 @@ struct TileMapArgs {
     unsigned tpp, m_tpp;          // tiles per plane
     unsigned pb, m_pb;            // tiles per column block (colblock > 0)
     unsigned m_gs_full, m_gs_tail;  // 8 * (block width): full blocks (or the whole width), the last (narrower) block
+    // triangular walk (tri != 0, make_tile_map_tri): tiles_m == tiles_n = T, tpp = T (T + 1) / 2, colblock = 0
+    int tri;                      // 0 = the rectangle, 1 = tm >= tn (lower), 2 = tm <= tn (upper: the lower walk transposed)
+    unsigned pr, m_pr;            // tiles of a pair of 4-row groups: 4 T
+    unsigned s_pairs;             // tiles of all pairs
+    int t0, th;                   // the middle rows that no pair takes: first tile-row, count (0 .. 7)
+    unsigned m_th;                // magic of th
 };
 inline unsigned map_magic(unsigned d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(0x100000000ull / d); }
 inline TileMapArgs make_tile_map(int tiles_m, int tiles_n, int colblock) {
@@ -107,6 +113,59 @@ __device__ __forceinline__ void udivmod_magic(unsigned x, unsigned d, unsigned M
     r = x - q * d;
     if (r >= d) ++q, r -= d;
 }
+// Triangular walk (gemmul8_syrk: only the tiles of one triangle of a symmetric product, diagonal tiles whole).  The unit is a group of 4
+// tile-rows a0 .. a0 + 3 cut at the diagonal: 4 (a0 + 1) tiles of its full columns 0 .. a0, tile-row fastest as in the rectangle (32
+// consecutive tiles = 4 x 8 tiles sharing 4 + 8 panels), then the 6 tiles of tile-rows a0 + 1 .. a0 + 3 right of them: 4 a0 + 10.  Long group p from
+// the bottom (a0 = T - 4 - 4 p) is paired with short group p from the top (a0 = 4 p - 1; the first one is tile-rows 0 .. 2 alone): 4 T tiles
+// whatever p is, so ONE magic division finds the pair, and a pair touches 8 tile-rows.  For T = 64 a pair is exactly one chunk of 256: the
+// 8 XCDs of a chunk share 8 A panels as in the rectangle; for other T chunks straddle pairs and touch the tile-rows of two or, below T = 64,
+// of 256 / (4 T) + 1 pairs.  The (T - 7) mod 8 middle tile-rows that no pair takes come last, walked the same way.  Every index is a tile of the
+// triangle: nothing is skipped, the producer and consumer waves keep their loop.
+inline TileMapArgs make_tile_map_tri(int tiles, int tri) {
+    TileMapArgs a{};
+    a.tiles_m = a.tiles_n = tiles;
+    a.tri = tri;
+    a.tpp = (unsigned)tiles * (unsigned)(tiles + 1) / 2;
+    a.m_tpp = map_magic(a.tpp);
+    const int np = tiles >= 7 ? (tiles - 7) / 8 + 1 : 0;
+    a.pr = 4u * (unsigned)tiles;
+    a.m_pr = map_magic(a.pr);
+    a.s_pairs = (unsigned)np * a.pr;
+    a.t0 = np ? 4 * np - 1 : 0;
+    a.th = tiles - a.t0 - 4 * np;
+    a.m_th = map_magic((unsigned)a.th);
+    return a;
+}
+// tile q of the h tile-rows a0 .. a0 + h - 1 cut at the diagonal (a0 = -1: tile-row -1 is empty); M = map_magic(h), unused for h == 4
+__device__ __forceinline__ void map_trapezoid(unsigned q, unsigned h, int a0, unsigned M, int& tm, int& tn) {
+    const unsigned full = h * (unsigned)(a0 + 1);
+    if (q < full) {
+        if (h == 4u) {
+            tm = a0 + (int)(q & 3u), tn = (int)(q >> 2);
+        } else {
+            unsigned c, r;
+            udivmod_magic(q, h, M, c, r);
+            tm = a0 + (int)r, tn = (int)c;
+        }
+        return;
+    }
+    const unsigned d = q - full;  // the triangle right of the full columns, row by row: 1, 2, .. tiles
+    const int i = 1 + (d >= 1u) + (d >= 3u) + (d >= 6u) + (d >= 10u) + (d >= 15u);
+    tm = a0 + i, tn = a0 + 1 + (int)d - i * (i - 1) / 2;
+}
+__device__ __forceinline__ void map_tile_tri(unsigned rem, const TileMapArgs& a, int& tm, int& tn) {
+    if (rem < a.s_pairs) {
+        unsigned p, q;
+        udivmod_magic(rem, a.pr, a.m_pr, p, q);
+        const unsigned ll = a.pr - 16u * p - 6u;  // the long group's tiles
+        if (q < ll) map_trapezoid(q, 4u, a.tiles_m - 4 - 4 * (int)p, 0u, tm, tn);
+        else map_trapezoid(q - ll, 4u, 4 * (int)p - 1, 0u, tm, tn);
+        return;
+    }
+    map_trapezoid(rem - a.s_pairs, (unsigned)a.th, a.t0, a.m_th, tm, tn);
+}
+// TRI: the instantiation may be launched with the triangular walk (the bound GEMM and the laboratory kernels never are: their code does not change)
+template <bool TRI = false>
 __device__ __forceinline__ TileMap map_tile(int bid, int nwg, const TileMapArgs a) {  // by value: the laboratory kernels read it from the kernel-argument address space
     {
         const int xcd = bid & 7, idx = bid >> 3;
@@ -122,6 +181,13 @@ __device__ __forceinline__ TileMap map_tile(int bid, int nwg, const TileMapArgs 
     unsigned plane, rem;
     udivmod_magic((unsigned)bid, a.tpp, a.m_tpp, plane, rem);
     t.plane = (int)plane;
+    if (TRI && a.tri != 0) {  // scalar branch, like colblock
+        int tm, tn;
+        map_tile_tri(rem, a, tm, tn);
+        t.tm = a.tri == 1 ? tm : tn;
+        t.tn = a.tri == 1 ? tn : tm;
+        return t;
+    }
     int tn0 = 0, w = a.tiles_n;
     unsigned m_gs = a.m_gs_full;
     if (a.colblock > 0) {

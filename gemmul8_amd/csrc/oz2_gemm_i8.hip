@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
                 for (int j = 0; j < 4; ++j) acc[i][j] = v4i{args.acc0, args.acc0, args.acc0, args.acc0};
         }
         for (int vb = blockIdx.x; vb < total; vb += G) {
-            const TileMap tmap = map_tile(vb, total, args.map);
+            const TileMap tmap = map_tile<EPI != EPI_MAX>(vb, total, args.map);
             const PlaneRef pref = (FUSE || EPI == EPI_MAX) ? PlaneRef{0, 0} : plane_ref(args, tmap.plane);  // (the bound GEMM looks its plane up at the epilogue: one value less across its K loop)
             const PlaneConsts pcon = (FUSE || EPI == EPI_MAX) ? PlaneConsts{} : plane_consts(args, pref);  // fetched here: the latency passes behind the K loop
             for (int pl = 0; pl < planes_per_tile; ++pl) {
@@ -348,7 +348,7 @@ __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args
     if (wm == 1) __builtin_amdgcn_s_barrier();  // trailing half: one segment behind
     int sA = 0;                                  // slot of A(g); B(g) sits in the next slot (mod 5)
     for (int vb = blockIdx.x; vb < total; vb += G) {
-        const TileMap tmap = map_tile(vb, total, args.map);
+        const TileMap tmap = map_tile<EPI != EPI_MAX>(vb, total, args.map);
         const PlaneRef pref = (FUSE || EPI == EPI_MAX) ? PlaneRef{0, 0} : plane_ref(args, tmap.plane);  // (the bound GEMM looks its plane up at the epilogue: one value less across its K loop)
         const PlaneConsts pcon = (FUSE || EPI == EPI_MAX) ? PlaneConsts{} : plane_consts(args, pref);  // fetched here: the latency passes behind the K loop
         for (int pl = 0; pl < planes_per_tile; ++pl) {
@@ -488,16 +488,18 @@ static hipError_t launch_sched(hipStream_t stream, GemmArgs& a, const std::condi
 // K-step-barrier form is faster by 10 / 7.5 / 4.7 / 2.4 % at k = 512 / 1024 / 2048 / 4096 (tile boundaries -- epilogue beside the
 // other half's first K-steps -- overlap better) and 2.4 % slower at k = 8192, where the board is power-bound and removing stalls
 // buys nothing while the s_sleep-paced LDS-DMA is a little less smooth than the barrier-paced one.
-template <int EPI> static hipError_t launch(hipStream_t stream, GemmArgs& a, int planes) {
+// tri: 0 = every tile, 1 / 2 = only the tiles of the lower / upper triangle of a square product (make_tile_map_tri; diagonal tiles whole)
+template <int EPI> static hipError_t launch(hipStream_t stream, GemmArgs& a, int planes, int tri = 0) {
     // batched call: the items' planes are one long plane sequence (item-major), the persistent tile loop runs over all of them
     a.ppi = planes;
     a.m_ppi = map_magic((unsigned)planes);
     a.bstride = g_batch.ws;
     planes *= (int)g_batch.batch;
-    a.total_tiles = planes * a.tiles_m * a.tiles_n;
+    if (tri != 0 && (EPI == EPI_MAX || a.tiles_m != a.tiles_n)) return hipErrorInvalidValue;
+    a.total_tiles = tri ? planes * (a.tiles_m * (a.tiles_m + 1) / 2) : planes * a.tiles_m * a.tiles_n;
     if (a.total_tiles <= 0) return hipSuccess;
-    a.colblock = map_colblock((size_t)a.tiles_n, (size_t)a.kp * (size_t)a.nseg);
-    a.map = make_tile_map(a.tiles_m, a.tiles_n, a.colblock);
+    a.colblock = tri ? 0 : map_colblock((size_t)a.tiles_n, (size_t)a.kp * (size_t)a.nseg);  // no column blocks in the triangular walk
+    a.map = tri ? make_tile_map_tri(a.tiles_m, tri) : make_tile_map(a.tiles_m, a.tiles_n, a.colblock);
     a.acc0 = (size_t)a.kp * (size_t)a.nseg <= 512 ? 0 : (int)0x80000000u;  // RED_ODD_SMALL needs |sum| < 2^23
     // (the bound GEMM keeps the ping-pong schedule at every k.  In round 2 its K-step-barrier instantiation spilled accumulators INSIDE
     // the MFMA loop; with the round-3 source it no longer does, but the single-plane launch still runs slower with it: bounds phase
@@ -531,7 +533,7 @@ static int nt_residue_planes(const GemmArgs& a, int planes, bool stream_out, boo
 }
 
 hipError_t launch_gemm_i8_mod(hipStream_t stream, const int8_t* A, const int8_t* B, size_t strideA, size_t strideB, size_t kp, size_t m,
-                              size_t n, int t_begin, int t_end, int8_t* out, size_t ldo, size_t strideO, bool stream_out) {
+                              size_t n, int t_begin, int t_end, int8_t* out, size_t ldo, size_t strideO, bool stream_out, int tri) {
     GemmArgs a{};
     a.A[0] = A;
     a.B[0] = B;
@@ -544,12 +546,12 @@ hipError_t launch_gemm_i8_mod(hipStream_t stream, const int8_t* A, const int8_t*
     a.strideO = strideO;
     fill_common(a, kp, m, n);
     a.nt_planes = nt_residue_planes(a, t_end - t_begin, stream_out);
-    return launch<EPI_MOD>(stream, a, t_end - t_begin);
+    return launch<EPI_MOD>(stream, a, t_end - t_begin, tri);
 }
 
 hipError_t launch_gemm_i8_cplx(hipStream_t stream, const int8_t* A, const int8_t* B, size_t strideA, size_t strideB, size_t kp, size_t m,
                                size_t n, int t_begin, int t_end, const int8_t* rx, const int8_t* ry, size_t strideR, int8_t* out,
-                               size_t ldo, size_t strideO) {
+                               size_t ldo, size_t strideO, int tri) {
     GemmArgs a{};
     a.A[0] = A;
     a.B[0] = B;
@@ -568,7 +570,7 @@ hipError_t launch_gemm_i8_cplx(hipStream_t stream, const int8_t* A, const int8_t
     // 2048, 7 moduli: the operand planes of the three parts never fit the Infinity Cache together, and the CRT finds more of the
     // interleaved plane there with the default policy -- so the combine launch keeps the default policy unless GEMMUL8_EPI_NT forces it)
     a.nt_planes = nt_residue_planes(a, t_end - t_begin, true, false);
-    return launch<EPI_CPLX>(stream, a, t_end - t_begin);
+    return launch<EPI_CPLX>(stream, a, t_end - t_begin, tri);
 }
 
 #ifndef OZ2_MAX_SMALL_TILES

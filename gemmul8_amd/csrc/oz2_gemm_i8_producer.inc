@@ -16,7 +16,7 @@
             return (const int8_t*)(((unsigned long long)hi << 32) | lo);
         };
 #ifndef OZ2_PRODUCER_MAP_TILE  // (the laboratory kernel that reads its arguments from the kernel-argument address space keeps the division form)
-#define OZ2_PRODUCER_MAP_TILE(vb_) map_tile((vb_), total, args.map)
+#define OZ2_PRODUCER_MAP_TILE(vb_) map_tile<EPI != EPI_MAX>((vb_), total, args.map)
 #endif
 #define PRODUCER_SET_TILE(vb_)                                                                                               \
     do {                                                                                                                     \

@@ -34,7 +34,8 @@
 //                                  per call    strided batches: one set of launches (default) in chunks of the given size, or lanes (emulate_batch)
 //   GEMMUL8_HOOK_ROCBLAS           per call    "1" = the rocBLAS entry points above act
 //   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
-//   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call)
+//   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call);
+//                                              a second line for hipblas{S,D,C,Z}syrk when one was seen
 //   GEMMUL8_HOOK_VERBOSE           per call    "1" = say why a hipblasLtMatmul call was left to the native routine
 //
 // Per-handle state under a mutex: three grow-only stream-ordered buffers (hipMallocAsync / hipFreeAsync), event hand-off when the handle's
@@ -61,11 +62,12 @@
 
 // The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
 // `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
-// then stays 0); the shim, which binds to this project's own libgemmul8.so, requires every entry.
+// then stays 0 -- and no gemmul8_syrk: every SYRK call then goes to the native routine); the shim, which binds to this project's own
+// libgemmul8.so, requires every entry.
 #define OZ2_ABI(X)                                                                                          \
     X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
     X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
-    X(set_nonfinite_mode, __attribute__((weak)))
+    X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak)))
 #ifndef OZ2_HOOK_SHIM
 #define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
 OZ2_ABI(X)
@@ -541,6 +543,7 @@ struct NativeScope {
 struct HookStats {
     std::atomic<unsigned long long> emu_calls{0}, nat_calls{0};
     std::atomic<unsigned long long> emu_mflops{0}, nat_mflops{0};  // 2 m n k batch / 1e6 (x 4 for complex), rounded down
+    std::atomic<unsigned long long> emu_syrk{0}, nat_syrk{0}, emu_syrk_mflops{0}, nat_syrk_mflops{0};  // hipblas?syrk: n (n + 1) k / 1e6 (x 4)
     static void dump();
     HookStats() { std::atexit(&HookStats::dump); }
 };
@@ -553,6 +556,9 @@ void HookStats::dump() {
     HookStats& h = hook_stats();
     std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu GEMM calls (%.3f TFLOP), native %llu GEMM calls through the hooked entry points (%.3f TFLOP)\n",
                  h.emu_calls.load(), h.emu_mflops.load() * 1e-6, h.nat_calls.load(), h.nat_mflops.load() * 1e-6);
+    if (h.emu_syrk.load() + h.nat_syrk.load())
+        std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu SYRK calls (%.3f TFLOP), native %llu SYRK calls through the hooked entry points (%.3f TFLOP)\n",
+                     h.emu_syrk.load(), h.emu_syrk_mflops.load() * 1e-6, h.nat_syrk.load(), h.nat_syrk_mflops.load() * 1e-6);
 }
 void count_call(bool emulated, const GemmCall& c) {
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
@@ -583,8 +589,9 @@ bool floor_model_declines(int dtype, double m, double n, double k, unsigned N, b
     const double tn = fm.n[0] + batch * (fm.n[1] * mn + fm.n[2] * mnk);
     return te > 0.95 * tn;
 }
-// quiet = a query (gemmul8_hook_would_emulate), not a call: no log line
-bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch = 1.0, bool quiet = false) {
+// quiet = a query (gemmul8_hook_would_emulate), not a call: no log line.  syrk = a SYRK call (m == n): a number is a floor on n (n + 1) k, `auto`
+// takes the GEMM model's decision for (n, n, k) -- native and emulated SYRK are both about half their GEMMs; no SYRK scan has been fitted.
+bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch = 1.0, bool quiet = false, bool syrk = false) {
     const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
     if (!s || !*s) return false;  // the reference's behaviour: every selected call is emulated
     bool declined;
@@ -593,14 +600,18 @@ bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast,
         declined = floor_model_declines(dtype, m, n, k, N, fast, backend, batch);
     } else {
         const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
-        declined = f && 2.0 * m * n * k < (double)f;
+        declined = f && (syrk ? n * (n + 1.0) * k : 2.0 * m * n * k) < (double)f;
     }
     if (declined && !quiet) {
-        static std::once_flag told;
-        std::call_once(told, [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cGEMM %.0f x %.0f x %.0f (batch %.0f, %u moduli%s) stays on the native routine -- "
-                                 "calls below the floor are NOT emulated (this message is printed once)\n",
-                         s, "SDCZ"[dtype], m, n, k, batch, N, backend == GEMMUL8_FP8 ? ", FP8 backend: cost x 1.75-2.1" : "");
+        static std::once_flag told[2];  // GEMM, SYRK
+        std::call_once(told[syrk], [&] {
+            if (syrk)
+                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cSYRK n = %.0f, k = %.0f (%u moduli) stays on the native routine -- calls below the "
+                                     "floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], n, k, N);
+            else
+                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cGEMM %.0f x %.0f x %.0f (batch %.0f, %u moduli%s) stays on the native routine -- "
+                                     "calls below the floor are NOT emulated (this message is printed once)\n",
+                             s, "SDCZ"[dtype], m, n, k, batch, N, backend == GEMMUL8_FP8 ? ", FP8 backend: cost x 1.75-2.1" : "");
         });
     }
     return declined;
@@ -693,6 +704,69 @@ bool try_emulate(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* sta
     if (tl_native_depth > 0) return false;  // inside a native pass-through of an outer hooked entry: the same call, already declined and counted
     const bool served = try_emulate_impl(handle, c, status, explicit_stream);
     count_call(served, c);
+    return served;
+}
+
+// ---- hipblas{S,D,C,Z}syrk (and the _64 twins): one triangle of alpha A A^T + beta C through gemmul8_syrk (no counterpart in the reference).
+// Selection: the type's GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, k > 2^17, a moduli count outside
+// the type's range (each said once), a fill mode or operation other than upper / lower and N / T, a dimension an int cannot hold, a library without
+// gemmul8_syrk.  GEMMUL8_MIN_FLOPS: below_floor's SYRK form.  GEMMUL8_DIST and the skip-scaling switches do not apply.
+bool try_syrk_impl(hipblasHandle_t handle, int dtype, int uplo, int trans, int n, int k, const void* alpha, const void* A, int lda, const void* beta,
+                   void* C, int ldc, hipblasStatus_t* status) {
+    const auto syrk = abi().syrk;
+    if (!syrk) return false;
+    if ((uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) || (trans != HIPBLAS_OP_N && trans != HIPBLAS_OP_T)) return false;
+    Selection s;
+    if (!selection_from_env(dtype, &s)) {
+        if (s.N != 0) {
+            static std::once_flag told;
+            std::call_once(told, [&] {
+                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %cSYRK calls use the native routine\n", kTypes[dtype].nmod, s.N,
+                             kTypes[dtype].max_moduli, "SDCZ"[dtype]);
+            });
+        }
+        return false;
+    }
+    if (s.backend == GEMMUL8_FP8 || k > kMaxK) {
+        static std::once_flag told[2];  // the backend, the k range: one notice each
+        std::call_once(told[s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] SYRK is emulated on the INT8 backend for k <= %d only (GEMMUL8_BACKEND=%d, k=%d): using the native routine "
+                                 "for such calls\n", kMaxK, s.backend, k);
+        });
+        return false;
+    }
+    if (below_floor(dtype, (double)n, (double)n, (double)k, s.N, s.fast, s.backend, 1.0, false, true)) return false;
+    LockedState l = lock_ordered(handle, nullptr);
+    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
+    const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)n, (size_t)n, (size_t)k, s.N, 0, 0, nullptr, nullptr);
+    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, "workC (syrk)"); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
+    const int rc = syrk(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, beta, C, (size_t)ldc, s.N, s.fast,
+                        l.sp->wC.ptr, nullptr);
+    if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
+        static std::once_flag warned;
+        std::call_once(warned, [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a SYRK call (status %d; type %d, n=%d k=%d): using the native routine for such calls\n", rc,
+                         dtype, n, k);
+        });
+        return false;
+    }
+    return *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR, true;
+}
+// counted front end; false = the native routine takes the call: also an empty product, a null pointer (the native routine reports it) or a
+// dimension an int cannot hold
+bool try_syrk(hipblasHandle_t handle, int dtype, int uplo, int trans, int64_t n, int64_t k, const void* alpha, const void* A, int64_t lda,
+              const void* beta, void* C, int64_t ldc, hipblasStatus_t* status) {
+    if (tl_native_depth > 0) return false;
+    const int64_t lim = 2147483647;
+    if (n <= 0 || k <= 0 || !alpha || !beta || !A || !C || n > lim || k > lim || lda > lim || ldc > lim) return false;
+    const bool served = try_syrk_impl(handle, dtype, uplo, trans, (int)n, (int)k, alpha, A, (int)lda, beta, C, (int)ldc, status);
+    static const bool on = env_one("GEMMUL8_HOOK_STATS");
+    if (on) {
+        HookStats& h = hook_stats();
+        const unsigned long long mf = (unsigned long long)((double)n * ((double)n + 1.0) * (double)k * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
+        (served ? h.emu_syrk : h.nat_syrk).fetch_add(1, std::memory_order_relaxed);
+        (served ? h.emu_syrk_mflops : h.nat_syrk_mflops).fetch_add(mf, std::memory_order_relaxed);
+    }
     return served;
 }
 
@@ -1128,11 +1202,20 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
         static const auto real_ = real<decltype(&FN)>(SYM);                                                                             \
         return rocblas_internal_gemm_hook<T, I>(real_, CODE, h, ta, tb, m, n, k, al, A, oa, lda, sa, B, ob, ldb, sb, be, C, oc, ldc, sc, bc); \
     }
+#define OZ2_SYRK_HOOK(NAME, T, I, CODE)                                                                                                 \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
+                         I lda, const T* beta, T* C, I ldc) {                                                                           \
+        hipblasStatus_t st;                                                                                                             \
+        if (try_syrk(handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, beta, C, ldc, &st)) return st;                          \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, beta, C, ldc);                      \
+    }
 // one stamp per type; Z / ZZ: the substitution indices of the mangled names, which differ between the real and the complex forms
 #define OZ2_TYPE_HOOKS(L, U, T, CODE, TAG, Z, ZZ, ZZZ)                                                                                   \
     OZ2_GEMM_HOOK(hipblas##U##gemm, T, int, CODE)                                                                                       \
     OZ2_GEMM_HOOK(hipblas##U##gemm_64, T, int64_t, CODE)                                                                                \
     OZ2_SB_HOOK(hipblas##U##gemmStridedBatched, T, CODE)                                                                                \
+    OZ2_SYRK_HOOK(hipblas##U##syrk, T, int, CODE)                                                                                       \
+    OZ2_SYRK_HOOK(hipblas##U##syrk_64, T, int64_t, CODE)                                                                                \
     OZ2_ROCBLAS_HOOK(rocblas_##L##gemm, rocblas_##L##gemm_strided_batched, T, CODE)                                                     \
     OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_##L##_32, T, int, CODE,                                                                        \
                          "_Z30rocblas_internal_gemm_templateI" TAG "E15rocblas_status_P15_rocblas_handle18rocblas_operation_" Z         \
@@ -1152,6 +1235,7 @@ OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
 #undef OZ2_ROCBLAS_INTERNAL
 #undef OZ2_ROCBLAS_HOOK
 #undef OZ2_GEMM_EX_HOOK
+#undef OZ2_SYRK_HOOK
 #undef OZ2_SB_HOOK
 #undef OZ2_GEMM_HOOK
 

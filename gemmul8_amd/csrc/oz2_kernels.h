@@ -34,11 +34,13 @@ inline thread_local BatchCtx g_batch;
 
 // ---- INT8 MFMA GEMM (oz2_gemm_i8.hip)
 hipError_t launch_gemm_i8_mod(hipStream_t stream, const int8_t* A, const int8_t* B, size_t strideA, size_t strideB, size_t kp, size_t m,
-                              size_t n, int t_begin, int t_end, int8_t* out, size_t ldo, size_t strideO, bool stream_out);
+                              size_t n, int t_begin, int t_end, int8_t* out, size_t ldo, size_t strideO, bool stream_out, int tri = 0);
                               // stream_out: the planes are read next by the CRT pass only (non-temporal stores allowed, see the definition)
+                              // tri (both launches): 1 / 2 = m == n and only the 256 x 256 tiles that touch the lower / upper triangle are computed
+                              // (the triangular walk of oz2_gemm_common.hpp; the other tiles of `out` are not written)
 hipError_t launch_gemm_i8_cplx(hipStream_t stream, const int8_t* A, const int8_t* B, size_t strideA, size_t strideB, size_t kp, size_t m,
                                size_t n, int t_begin, int t_end, const int8_t* rx, const int8_t* ry, size_t strideR, int8_t* out,
-                               size_t ldo, size_t strideO);
+                               size_t ldo, size_t strideO, int tri = 0);
 hipError_t launch_gemm_i8_max(hipStream_t stream, int nseg, const int8_t* const* A, const int8_t* const* B, size_t kp, size_t m, size_t n,
                               int* rowmax, int* colmax, int mid_seg = 0);
 
@@ -141,6 +143,10 @@ hipError_t launch_nonfinite_patch(hipStream_t stream, int dtype, int opA, int op
 hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, size_t m, size_t n, const void* Cmid, size_t ld_mid,
                       size_t plane_stride, const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta,
                       bool scalars_on_device, void* C, size_t ldc);
+// the same for one triangle of a square C (tri: 1 = i >= j, 2 = i <= j; INT8 residues): the other strict triangle of C and the residue tiles
+// behind it are neither read nor written; the entries of the triangle carry the bits launch_crt gives them
+hipError_t launch_crt_tri(hipStream_t stream, int dtype, unsigned N, size_t n, int tri, const void* Cmid, size_t ld_mid, size_t plane_stride,
+                          const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc);
 
 hipError_t launch_row_bias(hipStream_t stream, int dtype, size_t m, size_t n, void* D, size_t ldd, const void* bias);
 hipError_t launch_add_f64(hipStream_t stream, double* dst, const double* src, size_t count);  // dst += src (16-byte aligned arrays)

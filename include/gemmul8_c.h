@@ -139,6 +139,25 @@ GEMMUL8_API int gemmul8_gemm_batched(void *stream, int dtype, int backend, int o
                          long long strideB, const void *beta, void *C, size_t ldc, long long strideC, size_t batch,
                          unsigned num_moduli, int fastmode, void *work);
 
+/* Symmetric rank-k update of one triangle: C = alpha*A*A^T + beta*C (trans = N, A is n x k) or C = alpha*A^T*A + beta*C (trans = T, A is
+ * k x n; for the complex types too this is the plain transpose: SYRK, not HERK).  trans takes 0 / 1 or the hipblasOperation_t values 111 / 112,
+ * uplo GEMMUL8_LOWER / GEMMUL8_UPPER or the hipblasFillMode_t values 122 / 121.  All four element types, INT8 backend only (GEMMUL8_FP8:
+ * GEMMUL8_E_UNSUPPORTED -- the FP6 panel images of the two operands differ in layout).
+ *   - The triangle named by uplo, diagonal included, holds bit for bit what
+ *     gemmul8_gemm(dtype, GEMMUL8_INT8, trans, trans == N ? T : N, n, n, k, alpha, A, lda, A, lda, beta, C, ldc, ...) in non-finite mode 0 puts there;
+ *     no byte of the other strict triangle of C or of the ldc padding is read or written; beta == 0 never reads C.
+ *   - A is read, bounded and quantised once, the residue GEMMs run over the 256 x 256 tiles that touch the triangle only (about half the work of the
+ *     GEMM; the accurate mode's bound GEMM stays the full square).
+ *   - `work` holds gemmul8_work_size(is_complex, backend, n, n, k, num_moduli, 0, 0, NULL, NULL) bytes: the equivalent GEMM's workspace.
+ *   - alpha / beta host or device pointers, timers_ns, stream order and capture safety (timers_ns == NULL) as in gemmul8_gemm.
+ *   - n == 0 or k == 0: GEMMUL8_OK, C untouched.  Bad uplo / trans, a null pointer, k > 2^17: GEMMUL8_E_ARG.
+ *   - gemmul8_set_nonfinite_mode is ignored: the call behaves as mode 0.
+ * No counterpart in the reference (it emulates GEMM only). */
+enum { GEMMUL8_LOWER = 0, GEMMUL8_UPPER = 1 };
+GEMMUL8_API int gemmul8_syrk(void *stream, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void *alpha, const void *A,
+                             size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode, void *work,
+                             double *timers_ns);
+
 /* D(i, j) += bias[i] for a column-major m x n real matrix: the broadcast bias of a hipblasLtMatmul BIAS epilogue, applied by the hook after
  * the emulated GEMM (one more rounding than the vendor's fused form).  S / D only.  No counterpart in the reference. */
 GEMMUL8_API int gemmul8_add_row_bias(void *stream, int dtype, size_t m, size_t n, void *D, size_t ldd, const void *bias);

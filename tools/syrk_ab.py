@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Interleaved A/B of gemmul8_syrk against the GEMM it replaces, gemmul8_gemm(A, A^T), on one box: DSYRK n = k = 8192, n = 8192 k = 1024 and
+n = 16384 k = 512, 14 moduli, accurate and fast mode.  The GEMM side may come from another build of libgemmul8.so (--gemm-lib: e.g. the parent
+commit's), loaded in the same process; a second GEMM column of this build shows that the GEMM itself did not move.  Per-phase timers
+(timers_ns: scaling, low-precision GEMMs, CRT) of one extra call each are printed beside the medians.
+usage: python tools/syrk_ab.py [--gemm-lib parent/libgemmul8.so] [--rounds 9] [--shapes 8192x8192,8192x1024,16384x512] [--moduli 14] [--out FILE]"""
+import argparse
+import ctypes as C
+import json
+import os
+import shutil
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import gemmul8_amd as g
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--gemm-lib", default=None)
+ap.add_argument("--rounds", type=int, default=9)
+ap.add_argument("--shapes", default="8192x8192,8192x1024,16384x512")
+ap.add_argument("--moduli", type=int, default=14)
+ap.add_argument("--out", default=None)
+a = ap.parse_args()
+this = g.lib()
+other = None
+if a.gemm_lib:
+    cp = os.path.join(tempfile.mkdtemp(), "gemm_side.so")
+    shutil.copy(a.gemm_lib, cp)
+    other = C.CDLL(cp)
+    other.gemmul8_gemm.restype = C.c_int
+    other.gemmul8_gemm.argtypes = this.gemmul8_gemm.argtypes
+st = torch.cuda.current_stream().cuda_stream
+al, be = np.array([1.0]), np.array([0.0])
+N = a.moduli
+rows = []
+for shape in a.shapes.split(","):
+    n, k = (int(x) for x in shape.split("x"))
+    A = torch.randn((k, n), dtype=torch.float64, device="cuda")   # column-major n x k
+    Cout = torch.zeros((n, n), dtype=torch.float64, device="cuda")
+    work = torch.empty(g.work_size(False, g.INT8, n, n, k, N)[0], dtype=torch.uint8, device="cuda")
+    for fast in (0, 1):
+        def gemm(L, tm=None):
+            return L.gemmul8_gemm(st, g.D, g.INT8, 0, 1, n, n, k, al.ctypes.data, A.data_ptr(), n, A.data_ptr(), n, be.ctypes.data, Cout.data_ptr(), n, N,
+                                  fast, work.data_ptr(), None, None, 0, 0, 0, 0, tm)
+
+        def syrk(L, tm=None):
+            return L.gemmul8_syrk(st, g.D, g.INT8, 0, 0, n, k, al.ctypes.data, A.data_ptr(), n, be.ctypes.data, Cout.data_ptr(), n, N, fast, work.data_ptr(), tm)
+        legs = [("syrk", lambda tm=None: syrk(this, tm)), ("gemm", lambda tm=None: gemm(this, tm))]
+        if other is not None:
+            legs.append(("gemm_other_lib", lambda tm=None: gemm(other, tm)))
+        ts = {name: [] for name, _ in legs}
+        for r in range(a.rounds + 2):
+            for name, fn in legs:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                rc = fn()
+                e1.record()
+                torch.cuda.synchronize()
+                assert rc == 0, (name, rc)
+                if r >= 2:
+                    ts[name].append(e0.elapsed_time(e1))
+        rec = {"n": n, "k": k, "moduli": N, "mode": "fast" if fast else "accurate", "rounds": a.rounds}
+        for name, fn in legs:
+            t = sorted(ts[name])
+            tm = (C.c_double * 4)()
+            assert fn(tm) == 0
+            rec[name + "_ms"] = round(t[len(t) // 2], 4)
+            rec[name + "_min_ms"] = round(t[0], 4)
+            rec[name + "_phases_ms"] = {"scale": round(tm[0] * 1e-6, 4), "lowprec_gemm": round(tm[1] * 1e-6, 4), "crt": round(tm[3] * 1e-6, 4)}
+        base = rec.get("gemm_other_lib_ms", rec["gemm_ms"])
+        rec["syrk_over_gemm"] = round(rec["syrk_ms"] / base, 4)
+        rows.append(rec)
+        print(json.dumps(rec), flush=True)
+if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(0), "gemm_side": "other build" if other is not None else "this build", "results": rows}, f, indent=1)
