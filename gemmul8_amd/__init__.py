@@ -36,7 +36,7 @@ _lib = None
 
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
            "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
-           "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk"]
+           "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
 
@@ -122,6 +122,8 @@ def bind(L):
     L.gemmul8_syrk.restype = C.c_int
     L.gemmul8_syrk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    L.gemmul8_herk.restype = C.c_int
+    L.gemmul8_herk.argtypes = L.gemmul8_syrk.argtypes
     L.gemmul8_set_fp8_bound_mode.restype = C.c_int
     L.gemmul8_set_fp8_bound_mode.argtypes = [C.c_int]
     L.gemmul8_set_nonfinite_mode.restype = C.c_int
@@ -226,6 +228,41 @@ def syrk(A, num_moduli, uplo="L", trans="N", fastmode=False, alpha=1.0, beta=0.0
     rc = lib().gemmul8_syrk(st, _dtype_code(dt), INT8, UPLO[uplo], OPS[trans], n, k, al.ctypes.data, A.data_ptr(), lda, be.ctypes.data,
                             C_out.data_ptr(), C_out.shape[1], num_moduli, int(fastmode), work.data_ptr(), tm)
     check(rc, "gemmul8_syrk")
+    return C_out, (list(tm) if timers else None), work
+
+
+def herk(A, num_moduli, uplo="L", trans="N", fastmode=False, alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, timers=False):
+    """One triangle of C = alpha*A*A^H + beta*C (trans "N", A is n x k) or alpha*A^H*A + beta*C (trans "C", A is k x n) through gemmul8_herk:
+    complex types, INT8 backend, REAL alpha and beta.  Off the diagonal the triangle `uplo` is bit-identical to
+    `gemm(A, A, opA=trans, opB="C" if trans == "N" else "N", alpha=alpha, beta=beta)`; a diagonal entry holds that GEMM's real part and +0.0 as its
+    imaginary part (the incoming one is ignored); the other strict triangle of C_out is neither read nor written.
+    A and C_out are column-major matrices held as tensors of shape (cols, rows), as in `gemm`; a fresh C_out is zero-filled.
+    Returns (C, timers_ns or None, work)."""
+    import numpy as np
+    import torch
+    assert A.is_cuda and A.is_contiguous()
+    dt = A.dtype
+    if not dt.is_complex:
+        raise TypeError("herk takes complex64 / complex128 (use syrk for the real types)")
+    if trans not in ("N", "C"):
+        raise ValueError("trans is 'N' or 'C'")
+    if C_out is not None and (C_out.dtype != dt or not C_out.is_contiguous()):
+        raise TypeError("A and C_out must share one dtype and be contiguous")
+    lda = A.shape[1]
+    n, k = (lda, A.shape[0]) if trans == "N" else (A.shape[0], lda)
+    if C_out is None:
+        C_out = torch.zeros((n, n), dtype=dt, device=A.device)
+    if work is None:
+        tot, _, _ = work_size(True, INT8, n, n, k, num_moduli)
+        work = torch.empty(tot, dtype=torch.uint8, device=A.device)
+    np_dt = np.float32 if dt == torch.complex64 else np.float64
+    al = np.array([alpha], dtype=np_dt)
+    be = np.array([beta], dtype=np_dt)
+    tm = (C.c_double * 4)() if timers else None
+    st = stream if stream is not None else torch.cuda.current_stream(A.device).cuda_stream
+    rc = lib().gemmul8_herk(st, _dtype_code(dt), INT8, UPLO[uplo], OPS[trans], n, k, al.ctypes.data, A.data_ptr(), lda, be.ctypes.data,
+                            C_out.data_ptr(), C_out.shape[1], num_moduli, int(fastmode), work.data_ptr(), tm)
+    check(rc, "gemmul8_herk")
     return C_out, (list(tm) if timers else None), work
 
 

@@ -122,8 +122,12 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
         al[0] = ((const U*)a.alpha_dev)[0];
         be[0] = ((const U*)a.beta_dev)[0];
         if (CPLX) {
-            al[1] = ((const U*)a.alpha_dev)[1];
-            be[1] = ((const U*)a.beta_dev)[1];
+            if (TRI && a.herm) {  // real scalars: nothing lies behind them
+                al[1] = be[1] = (U)0;
+            } else {
+                al[1] = ((const U*)a.alpha_dev)[1];
+                be[1] = ((const U*)a.beta_dev)[1];
+            }
         }
         mode = 0;
     }
@@ -194,7 +198,8 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
             } else {
                 const U x = scalb<U>((U)crt_reduce(a, Sh[2 * r], Sl[2 * r]), sft);
                 const U y = scalb<U>((U)crt_reduce(a, Sh[2 * r + 1], Sl[2 * r + 1]), sft);
-                const U cx = oldc[2 * e], cy = oldc[2 * e + 1];
+                const bool hdiag = TRI && a.herm && row == col;  // Hermitian diagonal: the incoming imaginary part is 0 whatever the memory holds
+                const U cx = oldc[2 * e], cy = hdiag ? (U)0 : oldc[2 * e + 1];
                 switch (mode) {
                 case 1: outv[2 * e] = x, outv[2 * e + 1] = y; break;
                 case 2: outv[2 * e] = cx + x, outv[2 * e + 1] = cy + y; break;
@@ -205,6 +210,7 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
                     outv[2 * e + 1] = fmaU<U>(be[1], cx, fmaU<U>(be[0], cy, fmaU<U>(al[1], x, al[0] * y)));
                     break;
                 }
+                if (hdiag) outv[2 * e + 1] = (U)0;
             }
         }
     }
@@ -732,9 +738,11 @@ hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, si
 }
 
 hipError_t launch_crt_tri(hipStream_t stream, int dtype, unsigned N, size_t n, int tri, const void* Cmid, size_t ld_mid, size_t plane_stride,
-                          const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc) {
+                          const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc,
+                          bool herm) {
     if (n == 0) return hipSuccess;
     if (tri != 1 && tri != 2) return hipErrorInvalidValue;
+    if (herm && !is_complex(dtype)) return hipErrorInvalidValue;
     CrtArgs a{};
     a.Cmid = Cmid;
     a.ld_mid = ld_mid;
@@ -746,8 +754,19 @@ hipError_t launch_crt_tri(hipStream_t stream, int dtype, unsigned N, size_t n, i
     a.C = C;
     a.ldc = ldc;
     a.tri = tri;
+    a.herm = herm ? 1 : 0;
     fill_crt_tables(a, dtype, kINT8, N);
-    fill_crt_scalars(a, dtype, alpha, beta, scalars_on_device);
+    if (herm && !scalars_on_device) {  // real host scalars, widened to (alpha, 0), (beta, 0): mode selection and arithmetic are the complex GEMM's from here on
+        if (is_f32(dtype)) {
+            const float al[2] = {*(const float*)alpha, 0.0f}, be[2] = {*(const float*)beta, 0.0f};
+            fill_crt_scalars(a, dtype, al, be, false);
+        } else {
+            const double al[2] = {*(const double*)alpha, 0.0}, be[2] = {*(const double*)beta, 0.0};
+            fill_crt_scalars(a, dtype, al, be, false);
+        }
+    } else {
+        fill_crt_scalars(a, dtype, alpha, beta, scalars_on_device);
+    }
     const size_t rows_per_thread = OZ2_CRT_LB / (is_complex(dtype) ? 2 : 1);
     const size_t threads = ((n + rows_per_thread - 1) / rows_per_thread) * n;
     dim3 grid((unsigned)((threads + OZ2_CRT_BLOCK - 1) / OZ2_CRT_BLOCK));

@@ -25,6 +25,8 @@ struct CrtArgs {
     double q1[20], qh[20], ql[20];
     size_t bw, bc;  // batched launch (crt_kernel, gridDim.z items): bytes between the items' workspaces / between their C matrices
     int tri;        // crt_tri_kernel: 1 = only entries i >= j, 2 = only i <= j
+    int herm;       // crt_tri_kernel, complex types (gemmul8_herk): the scalars are real (device scalars: ONE real each), and on row == col the incoming
+                    // imaginary part counts as 0 and +0.0 is stored
 };
 
 // host side (oz2_crt.hip)

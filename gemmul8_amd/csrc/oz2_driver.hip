@@ -327,9 +327,14 @@ int gemmul8_scale_bounds(void* stream_, int dtype, int backend, int op_A, int op
     return scale_bounds_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, col_begin, col_end, L, skipA, skipB, false);
 }
 
+// where A's quantise launch also writes the conjugate twin's plane sets 1 and 2 (gemmul8_herk; QuantOperand::lo2)
+struct TwinPlanes {
+    int8_t* lo;
+    size_t plane_stride, part_stride;
+};
 static int scale_finish_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
                            const void* B, size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end, const gemmul8_layout* L, int skipA,
-                           int skipB, bool nf) {
+                           int skipB, bool nf, const TwinPlanes* twinA = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!L || !A || !B) return GEMMUL8_E_ARG;
     if (!moduli_ok(dtype, N) || t_end > N || t_begin > t_end) return GEMMUL8_E_NUM_MODULI;
@@ -346,6 +351,7 @@ static int scale_finish_nf(void* stream_, int dtype, int backend, int op_A, int 
     if (!skipA) oa = QuantOperand{kmajA, conjA, m, A, lda, L->sftA, (int8_t*)L->A_lo, L->sizeA, L->part_strideA, g_batch.sa, f6 ? L->mp : 0};
     if (!skipB) ob = QuantOperand{kmajB, conjB, n, B, ldb, L->sftB, (int8_t*)L->B_lo, L->sizeB, L->part_strideB, g_batch.sb, f6 ? n : 0};
     oa.nf = ob.nf = nf;
+    if (twinA) oa.lo2 = twinA->lo, oa.plane_stride2 = twinA->plane_stride, oa.part_stride2 = twinA->part_stride;
     if (fastmode) {
         OZ2_HIP(launch_fast_shift_pair(stream, dtype, backend, N, k, oa, ob));
         if (nf) {  // flagged rows / columns: sentinel shifts before the quantise reads them
@@ -381,12 +387,13 @@ int gemmul8_scale_finish(void* stream_, int dtype, int backend, int op_A, int op
 }
 
 static int scale_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda, const void* B,
-                    size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end, const gemmul8_layout* L, int skipA, int skipB, bool nf) {
+                    size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end, const gemmul8_layout* L, int skipA, int skipB, bool nf,
+                    const TwinPlanes* twinA = nullptr) {
     if (!fastmode) {
         int rc = scale_bounds_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, 0, n, L, skipA, skipB, nf);
         if (rc) return rc;
     }
-    return scale_finish_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB, nf);
+    return scale_finish_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB, nf, twinA);
 }
 
 int gemmul8_scale(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
@@ -650,15 +657,23 @@ int gemmul8_gemm(void* stream_, int dtype, int backend, int op_A, int op_B, size
 // |A| |A|^T is a symmetric integer matrix (rowmax == colmax), and residue and bound planes have one format for both sides -- so B's planes and
 // shifts ARE A's (tests/test_syrk_premise.py pins this on the oracle).  One operand pass (skipB), the residue GEMMs over the tiles of one
 // triangle, the CRT over its entries.  The accurate mode's bound GEMM stays the full square.
-int gemmul8_syrk(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda,
-                 const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
-    hipStream_t stream = (hipStream_t)stream_;
+//
+// ---- Hermitian rank-k update (herm; complex types).  op(A) op(A)^H is the GEMM (trans, trans == N ? C : N): shifts and bound planes are aliased as
+// above (the bounds take magnitudes), but only plane set 0 (Re) is shared.  The conjugated side holds the residues of -Im and of Re - Im where the
+// other side holds those of Im and Re + Im, and neither follows from the other's bytes (tests/test_herk_premise.py): the ONE operand pass writes
+// five plane sets -- A_lo parts 0 .. 2 as the equivalent GEMM's A side has them, and parts 1 and 2 of the GEMM's B_lo (its part 0 stays unwritten:
+// the right-hand Re planes are A_lo's).  Left panels come from A_lo, right panels from (A_lo part 0, B_lo parts 1, 2); the combine Cr = X - Y,
+// Ci = Z - X - Y does not change.  Im C is NOT bitwise antisymmetric (the CRT's mod-P reduction is not odd): every stored entry is computed as the
+// GEMM computes that entry, never mirrored.  The CRT's Hermitian arm takes real scalars and stores +0.0 as the diagonal's imaginary part.
+static int rank_k(bool herm, hipStream_t stream, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A,
+                  size_t lda, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
     if (timers_ns) timers_ns[0] = timers_ns[1] = timers_ns[2] = timers_ns[3] = 0.0;
     if (dtype < 0 || dtype > 3 || backend < 0 || backend > 1) return GEMMUL8_E_ARG;
+    if (herm && !is_complex(dtype)) return GEMMUL8_E_ARG;  // BLAS has no real HERK
     if (uplo == 122) uplo = GEMMUL8_LOWER;  // hipblasFillMode_t
     else if (uplo == 121) uplo = GEMMUL8_UPPER;
     trans = norm_op(trans);
-    if ((uplo != GEMMUL8_LOWER && uplo != GEMMUL8_UPPER) || (trans != 0 && trans != 1)) return GEMMUL8_E_ARG;
+    if ((uplo != GEMMUL8_LOWER && uplo != GEMMUL8_UPPER) || (trans != 0 && trans != (herm ? 2 : 1))) return GEMMUL8_E_ARG;
     if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
     if (!alpha || !beta || !A || !C || !work) return GEMMUL8_E_ARG;
     if (k > (size_t(1) << 17)) return GEMMUL8_E_ARG;
@@ -668,38 +683,42 @@ int gemmul8_syrk(void* stream_, int dtype, int backend, int uplo, int trans, siz
     gemmul8_layout L;
     int rc = gemmul8_get_layout(dtype, backend, n, n, k, N, work, nullptr, nullptr, 0, 0, &L);
     if (rc) return rc;
+    const TwinPlanes twin{(int8_t*)L.B_lo, L.sizeB, L.part_strideB};  // herm: the equivalent GEMM's B planes (rows unpadded), parts 1 and 2
     L.B_lo = L.A_lo, L.B_bound = L.A_bound, L.sftB = L.sftA, L.sizeB = L.sizeA, L.part_strideB = L.part_strideA;
     Timer* T = timers_ns ? thread_timer() : nullptr;
     if (T && hipEventRecord(T->ev[0], stream) != hipSuccess) {
         (void)hipGetLastError();
         T = nullptr;
     }
-    const int op_A = trans, op_B = trans == 0 ? 1 : 0;
-    rc = scale_nf(stream, dtype, backend, op_A, op_B, n, n, k, A, lda, A, lda, N, fastmode, 0, N, &L, 0, 1, false);
+    const int op_A = trans, op_B = trans == 0 ? (herm ? 2 : 1) : 0;
+    rc = scale_nf(stream, dtype, backend, op_A, op_B, n, n, k, A, lda, A, lda, N, fastmode, 0, N, &L, 0, 1, false, herm ? &twin : nullptr);
     if (rc) return rc;
     if (T) OZ2_HIP(hipEventRecord(T->ev[1], stream));
     const int tri = uplo == GEMMUL8_LOWER ? 1 : 2;
     const int8_t* A_lo = (const int8_t*)L.A_lo;
     if (!cplx) {
         OZ2_HIP(launch_gemm_i8_mod(stream, A_lo, A_lo, L.sizeA, L.sizeA, L.kp, n, n, 0, (int)N, (int8_t*)L.C_mid, L.mp, L.sizeC, true, tri));
-    } else {  // X = ArAr^T, Y = AiAi^T, Z = (Ar+Ai)(Ar+Ai)^T as in gemmul8_lowprec_gemm, each over the triangle's tiles
+    } else {  // X = ArAr^T, Y = AiAi^T, Z = (Ar+Ai)(Ar+Ai)^T as in gemmul8_lowprec_gemm, each over the triangle's tiles (herm: the right factors are Ar, -Ai, Ar-Ai)
         const size_t per_mod = 2 * L.sizeC;
         size_t chunk = L.scratch_bytes / per_mod;
         if (chunk == 0) return GEMMUL8_E_ARG;
         if (const size_t want = (size_t)knobs().cplx_chunk; want >= 1 && want < chunk) chunk = want;
         int8_t* rx = (int8_t*)L.scratch;
+        const size_t strideR = herm ? twin.plane_stride : L.sizeA;  // the right-hand Im and Re + Im planes
         for (unsigned t0 = 0; t0 < N; t0 += (unsigned)chunk) {
             const unsigned t1 = std::min<unsigned>(N, t0 + (unsigned)chunk);
             int8_t* ry = rx + (size_t)(t1 - t0) * L.sizeC;
             const int8_t *Ar = A_lo + (size_t)t0 * L.sizeA, *Ai = Ar + L.part_strideA, *As = Ar + 2 * L.part_strideA;
+            const int8_t* Bi = herm ? twin.lo + twin.part_stride + (size_t)t0 * twin.plane_stride : Ai;
+            const int8_t* Bs = herm ? twin.lo + 2 * twin.part_stride + (size_t)t0 * twin.plane_stride : As;
             OZ2_HIP(launch_gemm_i8_mod(stream, Ar, Ar, L.sizeA, L.sizeA, L.kp, n, n, (int)t0, (int)t1, rx, L.mp, L.sizeC, false, tri));
-            OZ2_HIP(launch_gemm_i8_mod(stream, Ai, Ai, L.sizeA, L.sizeA, L.kp, n, n, (int)t0, (int)t1, ry, L.mp, L.sizeC, false, tri));
-            OZ2_HIP(launch_gemm_i8_cplx(stream, As, As, L.sizeA, L.sizeA, L.kp, n, n, (int)t0, (int)t1, rx, ry, L.sizeC,
+            OZ2_HIP(launch_gemm_i8_mod(stream, Ai, Bi, L.sizeA, strideR, L.kp, n, n, (int)t0, (int)t1, ry, L.mp, L.sizeC, false, tri));
+            OZ2_HIP(launch_gemm_i8_cplx(stream, As, Bs, L.sizeA, strideR, L.kp, n, n, (int)t0, (int)t1, rx, ry, L.sizeC,
                                         (int8_t*)L.C_mid + (size_t)t0 * 2 * L.sizeC, L.mp, 2 * L.sizeC, tri));
         }
     }
     if (T) OZ2_HIP(hipEventRecord(T->ev[2], stream));
-    OZ2_HIP(launch_crt_tri(stream, dtype, N, n, tri, L.C_mid, L.mp, L.sizeC, L.sftA, L.sftA, alpha, beta, scalars_on_device(alpha), C, ldc));
+    OZ2_HIP(launch_crt_tri(stream, dtype, N, n, tri, L.C_mid, L.mp, L.sizeC, L.sftA, L.sftA, alpha, beta, scalars_on_device(alpha), C, ldc, herm));
     if (T) {
         OZ2_HIP(hipEventRecord(T->ev[3], stream));
         OZ2_HIP(hipEventSynchronize(T->ev[3]));
@@ -712,6 +731,16 @@ int gemmul8_syrk(void* stream_, int dtype, int backend, int uplo, int trans, siz
         timers_ns[3] = ms * 1e6;
     }
     return GEMMUL8_OK;
+}
+
+int gemmul8_syrk(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda,
+                 const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    return rank_k(false, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, beta, C, ldc, N, fastmode, work, timers_ns);
+}
+
+int gemmul8_herk(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda,
+                 const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    return rank_k(true, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, beta, C, ldc, N, fastmode, work, timers_ns);
 }
 
 int gemmul8_add_f64(void* stream_, double* dst, const double* src, size_t count) {

@@ -9,6 +9,8 @@
 //   hipblas{S,D,C,Z}gemm_64, hipblasGemmEx_64,                              yes (ROCm 7 ILP64 / WithFlags twins): the same contract; emulated when every
 //     hipblasGemmExWithFlags, hipblasGemmExWithFlags_64                       dimension fits an int, native otherwise
 //   hipblas{S,D,C,Z}gemmStridedBatched, hipblasGemmStridedBatchedEx         yes (torch.bmm): no early out, degenerate calls are the native routine's
+//   hipblas{S,D,C,Z}syrk(_64), hipblas{C,Z}herk(_64)                        yes: one triangle through gemmul8_syrk / gemmul8_herk (INT8 backend, k <= 2^17; HERK: real
+//                                                                             alpha / beta, N / C only); everything else is the native routine's, see try_syrk_impl
 //   hipblasLtMatmul, hipblasLtDestroy                                       yes (PyTorch's float32 matmuls): the plain case only, see lt_try
 //   hipblasLtMatrixLayoutCreate / SetAttribute / Destroy                    yes: record what a layout holds (hipBLASLt cannot be asked)
 //   rocblas_{s,d,c,z}gemm, rocblas_{s,d,c,z}gemm_strided_batched,           yes, only with GEMMUL8_HOOK_ROCBLAS=1: applications that call rocBLAS directly
@@ -35,7 +37,7 @@
 //   GEMMUL8_HOOK_ROCBLAS           per call    "1" = the rocBLAS entry points above act
 //   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
 //   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call);
-//                                              a second line for hipblas{S,D,C,Z}syrk when one was seen
+//                                              a second line for hipblas{S,D,C,Z}syrk and a third for hipblas{C,Z}herk when one was seen
 //   GEMMUL8_HOOK_VERBOSE           per call    "1" = say why a hipblasLtMatmul call was left to the native routine
 //
 // Per-handle state under a mutex: three grow-only stream-ordered buffers (hipMallocAsync / hipFreeAsync), event hand-off when the handle's
@@ -62,12 +64,12 @@
 
 // The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
 // `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
-// then stays 0 -- and no gemmul8_syrk: every SYRK call then goes to the native routine); the shim, which binds to this project's own
-// libgemmul8.so, requires every entry.
+// then stays 0 -- and no gemmul8_syrk / gemmul8_herk: every SYRK / HERK call then goes to the native routine); the shim, which binds to this
+// project's own libgemmul8.so, requires every entry.
 #define OZ2_ABI(X)                                                                                          \
     X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
     X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
-    X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak)))
+    X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak))) X(herk, __attribute__((weak)))
 #ifndef OZ2_HOOK_SHIM
 #define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
 OZ2_ABI(X)
@@ -543,7 +545,8 @@ struct NativeScope {
 struct HookStats {
     std::atomic<unsigned long long> emu_calls{0}, nat_calls{0};
     std::atomic<unsigned long long> emu_mflops{0}, nat_mflops{0};  // 2 m n k batch / 1e6 (x 4 for complex), rounded down
-    std::atomic<unsigned long long> emu_syrk{0}, nat_syrk{0}, emu_syrk_mflops{0}, nat_syrk_mflops{0};  // hipblas?syrk: n (n + 1) k / 1e6 (x 4)
+    // hipblas?syrk [0] / hipblas?herk [1]: n (n + 1) k / 1e6 (x 4)
+    std::atomic<unsigned long long> emu_syrk[2] = {{0}, {0}}, nat_syrk[2] = {{0}, {0}}, emu_syrk_mflops[2] = {{0}, {0}}, nat_syrk_mflops[2] = {{0}, {0}};
     static void dump();
     HookStats() { std::atexit(&HookStats::dump); }
 };
@@ -556,9 +559,11 @@ void HookStats::dump() {
     HookStats& h = hook_stats();
     std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu GEMM calls (%.3f TFLOP), native %llu GEMM calls through the hooked entry points (%.3f TFLOP)\n",
                  h.emu_calls.load(), h.emu_mflops.load() * 1e-6, h.nat_calls.load(), h.nat_mflops.load() * 1e-6);
-    if (h.emu_syrk.load() + h.nat_syrk.load())
-        std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu SYRK calls (%.3f TFLOP), native %llu SYRK calls through the hooked entry points (%.3f TFLOP)\n",
-                     h.emu_syrk.load(), h.emu_syrk_mflops.load() * 1e-6, h.nat_syrk.load(), h.nat_syrk_mflops.load() * 1e-6);
+    for (int herm = 0; herm < 2; ++herm)
+        if (h.emu_syrk[herm].load() + h.nat_syrk[herm].load())
+            std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu %s calls (%.3f TFLOP), native %llu %s calls through the hooked entry points (%.3f TFLOP)\n",
+                         h.emu_syrk[herm].load(), herm ? "HERK" : "SYRK", h.emu_syrk_mflops[herm].load() * 1e-6, h.nat_syrk[herm].load(),
+                         herm ? "HERK" : "SYRK", h.nat_syrk_mflops[herm].load() * 1e-6);
 }
 void count_call(bool emulated, const GemmCall& c) {
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
@@ -589,9 +594,10 @@ bool floor_model_declines(int dtype, double m, double n, double k, unsigned N, b
     const double tn = fm.n[0] + batch * (fm.n[1] * mn + fm.n[2] * mnk);
     return te > 0.95 * tn;
 }
-// quiet = a query (gemmul8_hook_would_emulate), not a call: no log line.  syrk = a SYRK call (m == n): a number is a floor on n (n + 1) k, `auto`
-// takes the GEMM model's decision for (n, n, k) -- native and emulated SYRK are both about half their GEMMs; no SYRK scan has been fitted.
-bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch = 1.0, bool quiet = false, bool syrk = false) {
+// quiet = a query (gemmul8_hook_would_emulate), not a call: no log line.  syrk = 1: a SYRK call, 2: a HERK call (m == n): a number is a floor on
+// n (n + 1) k, `auto` takes the GEMM model's decision for (n, n, k) -- native and emulated SYRK / HERK are both about half their GEMMs; no scan of
+// either has been fitted.
+bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch = 1.0, bool quiet = false, int syrk = 0) {
     const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
     if (!s || !*s) return false;  // the reference's behaviour: every selected call is emulated
     bool declined;
@@ -603,11 +609,11 @@ bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast,
         declined = f && (syrk ? n * (n + 1.0) * k : 2.0 * m * n * k) < (double)f;
     }
     if (declined && !quiet) {
-        static std::once_flag told[2];  // GEMM, SYRK
+        static std::once_flag told[3];  // GEMM, SYRK, HERK
         std::call_once(told[syrk], [&] {
             if (syrk)
-                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cSYRK n = %.0f, k = %.0f (%u moduli) stays on the native routine -- calls below the "
-                                     "floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], n, k, N);
+                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %c%s n = %.0f, k = %.0f (%u moduli) stays on the native routine -- calls below the "
+                                     "floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], syrk == 2 ? "HERK" : "SYRK", n, k, N);
             else
                 std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cGEMM %.0f x %.0f x %.0f (batch %.0f, %u moduli%s) stays on the native routine -- "
                                      "calls below the floor are NOT emulated (this message is printed once)\n",
@@ -707,46 +713,51 @@ bool try_emulate(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* sta
     return served;
 }
 
-// ---- hipblas{S,D,C,Z}syrk (and the _64 twins): one triangle of alpha A A^T + beta C through gemmul8_syrk (no counterpart in the reference).
+// ---- hipblas{S,D,C,Z}syrk and hipblas{C,Z}herk (and the _64 twins): one triangle of alpha A A^T + beta C through gemmul8_syrk, of alpha A A^H + beta C
+// (real alpha, beta) through gemmul8_herk (no counterpart in the reference).  One body; herm selects the entry point, the operations that are taken
+// (N / T, N / C) and the name in the log lines.
 // Selection: the type's GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, k > 2^17, a moduli count outside
-// the type's range (each said once), a fill mode or operation other than upper / lower and N / T, a dimension an int cannot hold, a library without
-// gemmul8_syrk.  GEMMUL8_MIN_FLOPS: below_floor's SYRK form.  GEMMUL8_DIST and the skip-scaling switches do not apply.
-bool try_syrk_impl(hipblasHandle_t handle, int dtype, int uplo, int trans, int n, int k, const void* alpha, const void* A, int lda, const void* beta,
-                   void* C, int ldc, hipblasStatus_t* status) {
-    const auto syrk = abi().syrk;
+// the type's range (each said once per routine), a fill mode or operation other than upper / lower and N / T (HERK: N / C), a dimension an int cannot
+// hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: below_floor's SYRK / HERK form.  GEMMUL8_DIST and the skip-scaling switches do not apply.
+bool try_syrk_impl(bool herm, hipblasHandle_t handle, int dtype, int uplo, int trans, int n, int k, const void* alpha, const void* A, int lda,
+                   const void* beta, void* C, int ldc, hipblasStatus_t* status) {
+    const auto syrk = herm ? abi().herk : abi().syrk;  // (one signature)
     if (!syrk) return false;
-    if ((uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) || (trans != HIPBLAS_OP_N && trans != HIPBLAS_OP_T)) return false;
+    const char* const name = herm ? "HERK" : "SYRK";
+    if ((uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) || (trans != HIPBLAS_OP_N && trans != (herm ? HIPBLAS_OP_C : HIPBLAS_OP_T)))
+        return false;
     Selection s;
     if (!selection_from_env(dtype, &s)) {
         if (s.N != 0) {
-            static std::once_flag told;
-            std::call_once(told, [&] {
-                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %cSYRK calls use the native routine\n", kTypes[dtype].nmod, s.N,
-                             kTypes[dtype].max_moduli, "SDCZ"[dtype]);
+            static std::once_flag told[2];
+            std::call_once(told[herm], [&] {
+                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %c%s calls use the native routine\n", kTypes[dtype].nmod, s.N,
+                             kTypes[dtype].max_moduli, "SDCZ"[dtype], name);
             });
         }
         return false;
     }
     if (s.backend == GEMMUL8_FP8 || k > kMaxK) {
-        static std::once_flag told[2];  // the backend, the k range: one notice each
-        std::call_once(told[s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] SYRK is emulated on the INT8 backend for k <= %d only (GEMMUL8_BACKEND=%d, k=%d): using the native routine "
-                                 "for such calls\n", kMaxK, s.backend, k);
+        static std::once_flag told[2][2];  // the backend, the k range: one notice each
+        std::call_once(told[herm][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for k <= %d only (GEMMUL8_BACKEND=%d, k=%d): using the native routine "
+                                 "for such calls\n", name, kMaxK, s.backend, k);
         });
         return false;
     }
-    if (below_floor(dtype, (double)n, (double)n, (double)k, s.N, s.fast, s.backend, 1.0, false, true)) return false;
+    if (below_floor(dtype, (double)n, (double)n, (double)k, s.N, s.fast, s.backend, 1.0, false, herm ? 2 : 1)) return false;
     LockedState l = lock_ordered(handle, nullptr);
     if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
     const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)n, (size_t)n, (size_t)k, s.N, 0, 0, nullptr, nullptr);
-    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, "workC (syrk)"); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
+    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, herm ? "workC (herk)" : "workC (syrk)"); st != HIPBLAS_STATUS_SUCCESS)
+        return *status = st, true;
     const int rc = syrk(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, beta, C, (size_t)ldc, s.N, s.fast,
                         l.sp->wC.ptr, nullptr);
     if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
-        static std::once_flag warned;
-        std::call_once(warned, [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a SYRK call (status %d; type %d, n=%d k=%d): using the native routine for such calls\n", rc,
-                         dtype, n, k);
+        static std::once_flag warned[2];
+        std::call_once(warned[herm], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a %s call (status %d; type %d, n=%d k=%d): using the native routine for such calls\n", name,
+                         rc, dtype, n, k);
         });
         return false;
     }
@@ -754,18 +765,18 @@ bool try_syrk_impl(hipblasHandle_t handle, int dtype, int uplo, int trans, int n
 }
 // counted front end; false = the native routine takes the call: also an empty product, a null pointer (the native routine reports it) or a
 // dimension an int cannot hold
-bool try_syrk(hipblasHandle_t handle, int dtype, int uplo, int trans, int64_t n, int64_t k, const void* alpha, const void* A, int64_t lda,
+bool try_syrk(bool herm, hipblasHandle_t handle, int dtype, int uplo, int trans, int64_t n, int64_t k, const void* alpha, const void* A, int64_t lda,
               const void* beta, void* C, int64_t ldc, hipblasStatus_t* status) {
     if (tl_native_depth > 0) return false;
     const int64_t lim = 2147483647;
     if (n <= 0 || k <= 0 || !alpha || !beta || !A || !C || n > lim || k > lim || lda > lim || ldc > lim) return false;
-    const bool served = try_syrk_impl(handle, dtype, uplo, trans, (int)n, (int)k, alpha, A, (int)lda, beta, C, (int)ldc, status);
+    const bool served = try_syrk_impl(herm, handle, dtype, uplo, trans, (int)n, (int)k, alpha, A, (int)lda, beta, C, (int)ldc, status);
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
     if (on) {
         HookStats& h = hook_stats();
         const unsigned long long mf = (unsigned long long)((double)n * ((double)n + 1.0) * (double)k * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
-        (served ? h.emu_syrk : h.nat_syrk).fetch_add(1, std::memory_order_relaxed);
-        (served ? h.emu_syrk_mflops : h.nat_syrk_mflops).fetch_add(mf, std::memory_order_relaxed);
+        (served ? h.emu_syrk : h.nat_syrk)[herm].fetch_add(1, std::memory_order_relaxed);
+        (served ? h.emu_syrk_mflops : h.nat_syrk_mflops)[herm].fetch_add(mf, std::memory_order_relaxed);
     }
     return served;
 }
@@ -1206,7 +1217,15 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
                          I lda, const T* beta, T* C, I ldc) {                                                                           \
         hipblasStatus_t st;                                                                                                             \
-        if (try_syrk(handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, beta, C, ldc, &st)) return st;                          \
+        if (try_syrk(false, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, beta, C, ldc, &st)) return st;                   \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, beta, C, ldc);                      \
+    }
+// hipblas{C,Z}herk: R = the real type of alpha and beta
+#define OZ2_HERK_HOOK(NAME, T, R, I, CODE)                                                                                              \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const R* alpha, const T* A, \
+                         I lda, const R* beta, T* C, I ldc) {                                                                           \
+        hipblasStatus_t st;                                                                                                             \
+        if (try_syrk(true, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, beta, C, ldc, &st)) return st;                    \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, beta, C, ldc);                      \
     }
 // one stamp per type; Z / ZZ: the substitution indices of the mangled names, which differ between the real and the complex forms
@@ -1227,6 +1246,10 @@ OZ2_TYPE_HOOKS(s, S, float, GEMMUL8_S, "f", "S3", "S6", "S4")
 OZ2_TYPE_HOOKS(d, D, double, GEMMUL8_D, "d", "S3", "S6", "S4")
 OZ2_TYPE_HOOKS(c, C, hipComplex, GEMMUL8_C, "19rocblas_complex_numIfE", "S5", "S8", "S6")
 OZ2_TYPE_HOOKS(z, Z, hipDoubleComplex, GEMMUL8_Z, "19rocblas_complex_numIdE", "S5", "S8", "S6")
+OZ2_HERK_HOOK(hipblasCherk, hipComplex, float, int, GEMMUL8_C)
+OZ2_HERK_HOOK(hipblasCherk_64, hipComplex, float, int64_t, GEMMUL8_C)
+OZ2_HERK_HOOK(hipblasZherk, hipDoubleComplex, double, int, GEMMUL8_Z)
+OZ2_HERK_HOOK(hipblasZherk_64, hipDoubleComplex, double, int64_t, GEMMUL8_Z)
 OZ2_GEMM_EX_HOOK(hipblasGemmEx, int)
 OZ2_GEMM_EX_HOOK(hipblasGemmEx_64, int64_t)
 OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags, int, flags)
@@ -1235,6 +1258,7 @@ OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
 #undef OZ2_ROCBLAS_INTERNAL
 #undef OZ2_ROCBLAS_HOOK
 #undef OZ2_GEMM_EX_HOOK
+#undef OZ2_HERK_HOOK
 #undef OZ2_SYRK_HOOK
 #undef OZ2_SB_HOOK
 #undef OZ2_GEMM_HOOK

@@ -107,6 +107,10 @@ struct QuantOperand {
     const int* fin_max = nullptr;
     float fin_log2P = 0.0f;
     bool nf = false;  // non-finite mode 1 (oz2_nonfinite.hip): a row whose shift is kNonfiniteSft gets zero planes (the finalize keeps the sentinel)
+    // gemmul8_herk (complex types, INT8 planes, the only operand of its launch): lo2 != nullptr = the same read also writes the conjugate twin's Im and
+    // Re + Im plane sets (the residues of -Im and Re - Im) to parts 1 and 2 of a second plane array with these strides; its part 0 is not written
+    int8_t* lo2 = nullptr;
+    size_t plane_stride2 = 0, part_stride2 = 0;
 };
 // FP8 backend: the residue planes are FP6 panel images whenever B's last row block fits its share of the reference's plane size
 // (16-row granules at 3/4 byte per element: n >= 45; 64 keeps whole wave tiles); GEMMUL8_FP8_PLANES=e4m3 keeps the e4m3 byte planes
@@ -144,9 +148,13 @@ hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, si
                       size_t plane_stride, const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta,
                       bool scalars_on_device, void* C, size_t ldc);
 // the same for one triangle of a square C (tri: 1 = i >= j, 2 = i <= j; INT8 residues): the other strict triangle of C and the residue tiles
-// behind it are neither read nor written; the entries of the triangle carry the bits launch_crt gives them
+// behind it are neither read nor written; the entries of the triangle carry the bits launch_crt gives them.
+// herm (complex types; gemmul8_herk): alpha / beta point to REAL scalars (host: widened to (alpha, 0), (beta, 0) here; device: one real each is read), an
+// off-diagonal entry carries the bits launch_crt gives it with the widened scalars, a diagonal entry that real part and +0.0 -- its incoming imaginary
+// part counts as 0 (a NaN there reaches neither component)
 hipError_t launch_crt_tri(hipStream_t stream, int dtype, unsigned N, size_t n, int tri, const void* Cmid, size_t ld_mid, size_t plane_stride,
-                          const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc);
+                          const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc,
+                          bool herm = false);
 
 hipError_t launch_row_bias(hipStream_t stream, int dtype, size_t m, size_t n, void* D, size_t ldd, const void* bias);
 hipError_t launch_add_f64(hipStream_t stream, double* dst, const double* src, size_t count);  // dst += src (16-byte aligned arrays)

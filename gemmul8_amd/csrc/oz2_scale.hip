@@ -157,6 +157,10 @@ struct StageArgs {
     unsigned f6_last;     // index of the plane's last 256-row block ...
     unsigned f6_rp_last;  // ... and its rows in the images (A: 256, B: its rows rounded up to 16)
     int nf;               // MODE_MOD, non-finite mode 1 (oz2_nonfinite.hip): a row whose shift is the sentinel gets zero planes, the finalize keeps it
+    // MODE_MOD, quantise_twin_kernel (gemmul8_herk; complex types, INT8 planes): the conjugate twin's Im and Re+Im plane sets -- the residues of -Im and
+    // of Re - Im of the SAME loaded elements -- go to parts 1 and 2 of a second plane array with strides of its own (its part 0 is not written)
+    int8_t* lo2;
+    size_t plane_stride2, part_stride2;
 };
 // item blockIdx.z of a batched launch: every workspace pointer moves by bw, the operand by bx (both 0 for a single GEMM).  The offsets
 // are applied at the few points of use: a modified COPY of the argument block lands in scratch memory (the quantise kernels ran 6x
@@ -325,7 +329,10 @@ template <bool WIDE> __device__ __forceinline__ int residue_from_small(int Ri, f
     return r;  // !WIDE: only the low byte is meaningful (the value is off by p * 2^22)
 }
 
-template <typename T> __device__ __forceinline__ void emit4_mod_float(const StageArgs& a, int8_t* out, const T (&v)[4], int s) {
+// TWIN (quantise_twin_kernel): out2 = the element's place in the twin's planes.  The twin's chain is the one a.conj selects, run on -xi: trunc, rint and the
+// exact fma are odd functions under round-to-nearest, so its level-1 remainder is -I to the bit and only the level-2 quotient (whose magic-number sum rounds
+// ties to even, and whose even-p tie is one-sided) is run again, on (-Ri, -Fi) -- the bytes a second pass over the operand with the other `conj` would write.
+template <typename T, bool TWIN = false> __device__ __forceinline__ void emit4_mod_float(const StageArgs& a, int8_t* out, [[maybe_unused]] int8_t* out2, const T (&v)[4], int s) {
     using E = ET<T>;
     double xr[4], xi[4];
     bool big = false;
@@ -381,12 +388,17 @@ template <typename T> __device__ __forceinline__ void emit4_mod_float(const Stag
                     }
                 }
                 int rr[4], ri[4], rs[4];
+                [[maybe_unused]] int rn[4], rd[4];  // TWIN: the residues of -Im and of Re - Im
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     rr[e] = residue_from_small<WIDE>(Rr[e], Fr[e], mc);
                     if constexpr (E::cplx) {
                         ri[e] = residue_from_small<WIDE>(Ri[e], Fi[e], mc);
                         rs[e] = WIDE ? wrapping(rr[e] + ri[e], mc.p) : wrapping((int)(int8_t)rr[e] + (int)(int8_t)ri[e], mc.p);
+                        if constexpr (TWIN && !WIDE) {
+                            rn[e] = residue_from_small<WIDE>(-Ri[e], -Fi[e], mc);
+                            rd[e] = wrapping((int)(int8_t)rr[e] + (int)(int8_t)rn[e], mc.p);
+                        }
                     }
                 }
                 if constexpr (WIDE) {
@@ -414,12 +426,22 @@ template <typename T> __device__ __forceinline__ void emit4_mod_float(const Stag
                     if constexpr (E::cplx) {
                         *(unsigned*)(o + a.part_stride) = pack(ri);
                         *(unsigned*)(o + 2 * a.part_stride) = pack(rs);
+                        if constexpr (TWIN) {
+                            int8_t* o2 = out2 + (size_t)tt * a.plane_stride2;
+                            *(unsigned*)(o2 + a.part_stride2) = pack(rn);
+                            *(unsigned*)(o2 + 2 * a.part_stride2) = pack(rd);
+                        }
                     }
                 }
             }
         }
     };
     const bool anybig = __any(big);
+    if constexpr (TWIN) {  // INT8 planes only
+        if (anybig) run.template operator()<false, true>();
+        else run.template operator()<false, false>();
+        return;
+    }
     if (a.backend == kFP8) {
         if (anybig) run.template operator()<true, true>();
         else run.template operator()<true, false>();
@@ -429,7 +451,7 @@ template <typename T> __device__ __forceinline__ void emit4_mod_float(const Stag
     }
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool TWIN = false>
 __device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0, const T (&vin)[4], int s) {
     using E = ET<T>;
     T v[4] = {vin[0], vin[1], vin[2], vin[3]};
@@ -488,12 +510,12 @@ __device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0,
             *(unsigned*)(out + 2 * a.part_stride) = wd;
         }
     } else {
-        emit4_mod_float<T>(a, out, v, s);
+        emit4_mod_float<T, TWIN>(a, out, TWIN ? a.lo2 + OZ2_ZW + row * a.kp + k0 : nullptr, v, s);
     }
 }
 
 // K-major operand: one 256-thread block per row; thread = 4 consecutive k per 1024-wide sweep
-template <typename T, int MODE>
+template <typename T, int MODE, bool TWIN = false>
 __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsigned bid) {
     using E = ET<T>;
     using U = typename E::U;
@@ -511,7 +533,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
             const int s = OZ2_ROW_SHIFT(a, row, bid == rg * nks && (threadIdx.x & 31) == 0);
             T v[4];
             load4<T>(x, k0, a.k, v);
-            emit4<T, MODE>(a, row, k0, v, s);
+            emit4<T, MODE, TWIN>(a, row, k0, v, s);
             return;
         }
     }
@@ -526,7 +548,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
         const int s = OZ2_ROW_SHIFT(a, row, k0 == 0);
         T v[4];
         load4<T>(x, k0, a.k, v);
-        emit4<T, MODE>(a, row, k0, v, s);
+        emit4<T, MODE, TWIN>(a, row, k0, v, s);
         return;
     }
     const size_t row = bid;
@@ -565,7 +587,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
 #pragma unroll
             for (int it = 0; it < NC; ++it) {
                 const size_t k0 = (size_t)threadIdx.x * 4 + (size_t)it * 1024;
-                if (k0 < a.kp) emit4<T, MODE>(a, row, k0, vb[it], s);
+                if (k0 < a.kp) emit4<T, MODE, TWIN>(a, row, k0, vb[it], s);
             }
             return;
         }
@@ -601,7 +623,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
     for (size_t k0 = (size_t)threadIdx.x * 4; k0 < a.kp; k0 += 1024) {
         T v[4];
         load4<T>(x, k0, a.k, v);
-        emit4<T, MODE>(a, row, k0, v, s);
+        emit4<T, MODE, TWIN>(a, row, k0, v, s);
     }
 }
 
@@ -617,7 +639,7 @@ template <typename T> struct StageTile {
     static constexpr int TR = sizeof(T) == 4 ? 32 : sizeof(T) == 16 ? 8 : OZ2_STAGE_TR8;
     static constexpr int TK = 128;
 };
-template <typename T, int MODE>
+template <typename T, int MODE, bool TWIN = false>
 __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const unsigned bid) {
     using E = ET<T>;
     using U = typename E::U;
@@ -726,7 +748,7 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
         T v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = tile[rl][c * 4 + e];
-        emit4<T, MODE>(a, row, kb + c * 4, v, s);
+        emit4<T, MODE, TWIN>(a, row, kb + c * 4, v, s);
     }
 }
 
@@ -758,6 +780,13 @@ template <typename T> __global__ void __launch_bounds__(256) quantise_pair_kerne
         if (kmB) stage_kmajor_body<T, MODE_MOD>(b, blockIdx.x - nA);
         else stage_strided_body<T, MODE_MOD>(b, blockIdx.x - nA);
     }
+}
+// gemmul8_herk: ONE complex operand, whose every loaded element leaves as five plane sets -- Re, Im, Re + Im at a.lo as above, and the conjugate
+// twin's -Im and Re - Im at a.lo2 (emit4_mod_float<T, true>): the planes of both sides of op(A) op(A)^H from one read of A
+template <typename T> __global__ void __launch_bounds__(256) quantise_twin_kernel(const StageArgs a, const int km) {
+    static_assert(ET<T>::cplx, "complex operands");
+    if (km) stage_kmajor_body<T, MODE_MOD, true>(a, blockIdx.x);
+    else stage_strided_body<T, MODE_MOD, true>(a, blockIdx.x);
 }
 static_assert(2 * sizeof(StageArgs) + 16 <= 4096, "two argument blocks must fit the 4 KiB kernel-argument segment");
 
@@ -1187,9 +1216,24 @@ static StageArgs quantise_args(int backend, int t_begin, int t_end, size_t k, si
     return a;
 }
 
+static hipError_t launch_quantise_twin(hipStream_t stream, int dtype, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A) {
+    StageArgs a = quantise_args(kINT8, t_begin, t_end, k, kp, A);
+    a.lo2 = A.lo2, a.plane_stride2 = A.plane_stride2, a.part_stride2 = A.part_stride2;
+    const size_t nA = dtype == kC32 ? stage_blocks<float2, MODE_MOD>(A.kmajor, a) : stage_blocks<double2, MODE_MOD>(A.kmajor, a);
+    if (nA > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)nA, 1, g_batch.batch);
+    if (dtype == kC32) hipLaunchKernelGGL(quantise_twin_kernel<float2>, grid, dim3(256), 0, stream, a, (int)A.kmajor);
+    else hipLaunchKernelGGL(quantise_twin_kernel<double2>, grid, dim3(256), 0, stream, a, (int)A.kmajor);
+    return hipGetLastError();
+}
+
 hipError_t launch_quantise_pair(hipStream_t stream, int dtype, int backend, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A,
                                 const QuantOperand& B) {
     if ((A.rows == 0 && B.rows == 0) || t_end <= t_begin) return hipSuccess;
+    if (A.lo2 || B.lo2) {  // the twin form: A alone, complex, INT8 byte planes, mode 0
+        if (B.rows || B.lo2 || A.rows == 0 || !is_complex(dtype) || backend != kINT8 || A.f6_rows || A.nf) return hipErrorInvalidValue;
+        return launch_quantise_twin(stream, dtype, t_begin, t_end, k, kp, A);
+    }
     const StageArgs a = quantise_args(backend, t_begin, t_end, k, kp, A), b = quantise_args(backend, t_begin, t_end, k, kp, B);
     switch (dtype) {
     case kF32: return launch_quantise_stage<float>(stream, A.kmajor, a, B.kmajor, b);

@@ -158,6 +158,33 @@ GEMMUL8_API int gemmul8_syrk(void *stream, int dtype, int backend, int uplo, int
                              size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode, void *work,
                              double *timers_ns);
 
+/* Hermitian rank-k update of one triangle: C = alpha*A*A^H + beta*C (trans = N, A is n x k) or C = alpha*A^H*A + beta*C (trans = C, A is k x n).
+ * dtype GEMMUL8_C / GEMMUL8_Z only (S / D: GEMMUL8_E_ARG -- BLAS has no real HERK); trans takes 0 / 2 or the hipblasOperation_t values 111 / 113
+ * (T, 1 / 112: GEMMUL8_E_ARG); uplo as in gemmul8_syrk.  alpha and beta point to REAL scalars (float for C, double for Z), host or device, detected
+ * as elsewhere.  INT8 backend only (GEMMUL8_FP8: GEMMUL8_E_UNSUPPORTED).
+ *   - Every OFF-DIAGONAL entry of the triangle named by uplo holds, bit for bit, what
+ *     gemmul8_gemm(dtype, GEMMUL8_INT8, trans, trans == N ? C : N, n, n, k, (alpha, 0), A, lda, A, lda, (beta, 0), C, ldc, ...) in non-finite mode 0
+ *     puts there.
+ *   - A DIAGONAL entry holds that GEMM's real part bit for bit and +0.0 as its imaginary part.  The incoming imaginary part of a diagonal entry counts
+ *     as 0 whatever the memory holds: a NaN there reaches neither component.
+ *   - No byte of the other strict triangle of C or of the ldc padding is read or written; beta == 0 never reads C.
+ *   - A is read, bounded and quantised ONCE.  HERK is not SYRK with a flag: in the GEMM of A with its own conjugate transpose the two sides share their
+ *     shifts, their bound planes and their Re residue planes, but where one side holds the residues of Im and Re + Im the conjugated side holds those of
+ *     -Im (the byte-wise negation; for the modulus 256 the byte -128 maps to itself) and of Re - Im, which no plane of the other side has.  The one
+ *     operand pass therefore writes five plane sets: Re, Im, Re + Im into A's planes and -Im, Re - Im into parts 1 and 2 of the equivalent GEMM's B
+ *     planes (that GEMM's workspace layout; part 0 of its B planes stays unwritten).
+ *   - The result is NOT bitwise Hermitian: Re C of the equivalent GEMM is bitwise symmetric and its diagonal's imaginary part is exactly zero, but Im C
+ *     is not bitwise antisymmetric (the CRT's reduction modulo P is not an odd function).  Every stored entry is therefore computed as the GEMM computes
+ *     that entry -- row i of the left factor, row j of the right one -- and never mirrored or negated from the other triangle
+ *     (tests/test_herk_premise.py pins all of this on the oracle).
+ *   - The residue GEMMs run over the 256 x 256 tiles that touch the triangle only; the accurate mode's bound GEMM stays the full square.
+ *   - `work`, timers_ns, stream order, capture safety, n == 0 or k == 0, null pointers and k > 2^17 as in gemmul8_syrk.
+ *   - gemmul8_set_nonfinite_mode is ignored: the call behaves as mode 0.
+ * No counterpart in the reference (it emulates GEMM only). */
+GEMMUL8_API int gemmul8_herk(void *stream, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void *alpha, const void *A,
+                             size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode, void *work,
+                             double *timers_ns);
+
 /* D(i, j) += bias[i] for a column-major m x n real matrix: the broadcast bias of a hipblasLtMatmul BIAS epilogue, applied by the hook after
  * the emulated GEMM (one more rounding than the vendor's fused form).  S / D only.  No counterpart in the reference. */
 GEMMUL8_API int gemmul8_add_row_bias(void *stream, int dtype, size_t m, size_t n, void *D, size_t ldd, const void *bias);

@@ -3,7 +3,8 @@
 n = 16384 k = 512, 14 moduli, accurate and fast mode.  The GEMM side may come from another build of libgemmul8.so (--gemm-lib: e.g. the parent
 commit's), loaded in the same process; a second GEMM column of this build shows that the GEMM itself did not move.  Per-phase timers
 (timers_ns: scaling, low-precision GEMMs, CRT) of one extra call each are printed beside the medians.
-usage: python tools/syrk_ab.py [--gemm-lib parent/libgemmul8.so] [--rounds 9] [--shapes 8192x8192,8192x1024,16384x512] [--moduli 14] [--out FILE]"""
+--herk: gemmul8_herk against gemmul8_gemm(A, A^H) instead -- ZHERK n = k = 8192 at 20 moduli and CHERK at 13 (--shapes / --moduli / --types override).
+usage: python tools/syrk_ab.py [--herk] [--gemm-lib parent/libgemmul8.so] [--rounds 9] [--shapes 8192x8192,8192x1024,16384x512] [--moduli 14] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -21,8 +22,10 @@ import gemmul8_amd as g
 ap = argparse.ArgumentParser()
 ap.add_argument("--gemm-lib", default=None)
 ap.add_argument("--rounds", type=int, default=9)
-ap.add_argument("--shapes", default="8192x8192,8192x1024,16384x512")
-ap.add_argument("--moduli", type=int, default=14)
+ap.add_argument("--herk", action="store_true")
+ap.add_argument("--shapes", default=None)
+ap.add_argument("--moduli", type=int, default=None, help="default: 14 (SYRK); --herk: 20 for Z, 13 for C")
+ap.add_argument("--types", default=None, help="SYRK: D; --herk: Z,C")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 this = g.lib()
@@ -34,22 +37,30 @@ if a.gemm_lib:
     other.gemmul8_gemm.restype = C.c_int
     other.gemmul8_gemm.argtypes = this.gemmul8_gemm.argtypes
 st = torch.cuda.current_stream().cuda_stream
-al, be = np.array([1.0]), np.array([0.0])
-N = a.moduli
+TYPES = {"D": (g.D, torch.float64, np.float64, np.float64), "Z": (g.Z, torch.complex128, np.complex128, np.float64),
+         "C": (g.Cx, torch.complex64, np.complex64, np.float32)}   # code, tensor type, GEMM scalar type, rank-k scalar type
+shapes = a.shapes or ("8192x8192" if a.herk else "8192x8192,8192x1024,16384x512")
 rows = []
-for shape in a.shapes.split(","):
+for ty, shape in ((t, s) for t in (a.types or ("Z,C" if a.herk else "D")).split(",") for s in shapes.split(",")):
+    code, tdt, gdt, rdt = TYPES[ty]
+    N = a.moduli or ((20 if ty == "Z" else 13) if a.herk else 14)
+    al, be = np.array([1.0], dtype=gdt), np.array([0.0], dtype=gdt)      # the GEMM's scalars (complex for Z / C)
+    ral, rbe = np.array([1.0], dtype=rdt), np.array([0.0], dtype=rdt)    # SYRK: the same type; HERK: real
     n, k = (int(x) for x in shape.split("x"))
-    A = torch.randn((k, n), dtype=torch.float64, device="cuda")   # column-major n x k
-    Cout = torch.zeros((n, n), dtype=torch.float64, device="cuda")
-    work = torch.empty(g.work_size(False, g.INT8, n, n, k, N)[0], dtype=torch.uint8, device="cuda")
+    A = torch.randn((k, n), dtype=tdt, device="cuda")   # column-major n x k
+    Cout = torch.zeros((n, n), dtype=tdt, device="cuda")
+    work = torch.empty(g.work_size(tdt.is_complex, g.INT8, n, n, k, N)[0], dtype=torch.uint8, device="cuda")
     for fast in (0, 1):
         def gemm(L, tm=None):
-            return L.gemmul8_gemm(st, g.D, g.INT8, 0, 1, n, n, k, al.ctypes.data, A.data_ptr(), n, A.data_ptr(), n, be.ctypes.data, Cout.data_ptr(), n, N,
-                                  fast, work.data_ptr(), None, None, 0, 0, 0, 0, tm)
+            return L.gemmul8_gemm(st, code, g.INT8, 0, 2 if a.herk else 1, n, n, k, al.ctypes.data, A.data_ptr(), n, A.data_ptr(), n, be.ctypes.data,
+                                  Cout.data_ptr(), n, N, fast, work.data_ptr(), None, None, 0, 0, 0, 0, tm)
 
         def syrk(L, tm=None):
-            return L.gemmul8_syrk(st, g.D, g.INT8, 0, 0, n, k, al.ctypes.data, A.data_ptr(), n, be.ctypes.data, Cout.data_ptr(), n, N, fast, work.data_ptr(), tm)
-        legs = [("syrk", lambda tm=None: syrk(this, tm)), ("gemm", lambda tm=None: gemm(this, tm))]
+            fn = L.gemmul8_herk if a.herk else L.gemmul8_syrk
+            return fn(st, code, g.INT8, 0, 0, n, k, (ral if a.herk else al).ctypes.data, A.data_ptr(), n, (rbe if a.herk else be).ctypes.data, Cout.data_ptr(), n, N,
+                      fast, work.data_ptr(), tm)
+        rk = "herk" if a.herk else "syrk"
+        legs = [(rk, lambda tm=None: syrk(this, tm)), ("gemm", lambda tm=None: gemm(this, tm))]
         if other is not None:
             legs.append(("gemm_other_lib", lambda tm=None: gemm(other, tm)))
         ts = {name: [] for name, _ in legs}
@@ -63,7 +74,7 @@ for shape in a.shapes.split(","):
                 assert rc == 0, (name, rc)
                 if r >= 2:
                     ts[name].append(e0.elapsed_time(e1))
-        rec = {"n": n, "k": k, "moduli": N, "mode": "fast" if fast else "accurate", "rounds": a.rounds}
+        rec = {"type": ty, "n": n, "k": k, "moduli": N, "mode": "fast" if fast else "accurate", "rounds": a.rounds}
         for name, fn in legs:
             t = sorted(ts[name])
             tm = (C.c_double * 4)()
@@ -72,7 +83,7 @@ for shape in a.shapes.split(","):
             rec[name + "_min_ms"] = round(t[0], 4)
             rec[name + "_phases_ms"] = {"scale": round(tm[0] * 1e-6, 4), "lowprec_gemm": round(tm[1] * 1e-6, 4), "crt": round(tm[3] * 1e-6, 4)}
         base = rec.get("gemm_other_lib_ms", rec["gemm_ms"])
-        rec["syrk_over_gemm"] = round(rec["syrk_ms"] / base, 4)
+        rec[rk + "_over_gemm"] = round(rec[rk + "_ms"] / base, 4)
         rows.append(rec)
         print(json.dumps(rec), flush=True)
 if a.out:
