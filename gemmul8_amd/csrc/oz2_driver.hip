@@ -97,6 +97,7 @@ static Knobs parse_knobs() {
     if (const char* e = getenv("GEMMUL8_FP8_FUSED"); e && e[0] == '0') k.fp8_fused = 0;
     if (const char* e = getenv("GEMMUL8_FP8_PLANES")) k.fp8_planes = e[0] == 'e' ? 1 : 0;
     if (const char* e = getenv("GEMMUL8_SCALE_FOLD"); e && e[0] == '0') k.scale_fold = 0;
+    if (const char* e = getenv("GEMMUL8_BOUNDS_ONE_READ"); e && (e[0] == '0' || e[0] == '1') && !e[1]) k.bounds_one_read = e[0] - '0';
     if (const char* e = getenv("GEMMUL8_CRT_PANELS"); e && atoi(e) > 1) {
         k.crt_panels = std::min(atoi(e), 256);
         k.crt_panels_ring = e[strlen(e) - 1] == 'r';
@@ -229,6 +230,8 @@ static int scale_scratch(const gemmul8_layout* L, size_t n, int** rowmax, int** 
 }
 
 // nf: non-finite mode 1 (gemmul8_set_nonfinite_mode) -- passed down from the whole-call entry points only; the phase-level entry points run mode 0
+// rows from which a row-strided operand takes the one-read extract (16 / 32 rows per workgroup): measured, DESIGN.md 3.4
+constexpr size_t kOneReadMinRows = 8192;
 static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
                            const void* B, size_t ldb, unsigned N, size_t col_begin, size_t col_end, const gemmul8_layout* L, int skipA, int skipB,
                            bool nf) {
@@ -255,15 +258,26 @@ static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int 
     // and the two extracts as launches of their own (the round-5 launch count).
     const bool runA = !skipA, runB = !skipB;
     const size_t ub = is_f32(dtype) ? 4 : 8;  // bytes of a row maximum
-    const size_t srA = runA && !kmajA ? L->mp : 0, srB = runB && !kmajB ? np : 0;  // padded row counts of the operands that need the pass
+    // a row-strided operand with enough row panels to keep the memory system busy takes the one-read extract (no row-maxima pass: DESIGN.md 3.4)
+    const int force1 = knobs().bounds_one_read;
+    // (by default only 16-byte aligned operands: its loads are pipelined where every 16-byte row group is aligned, an unaligned operand walks tile by tile)
+    const size_t esz = is_f32(dtype) ? 4 : 8;
+    auto one_read = [&](bool run, bool kmaj, size_t rows, const void* X, size_t ld) {
+        const bool aligned = ((reinterpret_cast<uintptr_t>(X) | (ld * esz)) & 15u) == 0;
+        return run && !kmaj && extract_one_read_ok(dtype, backend, L->kp) && (force1 < 0 ? rows >= kOneReadMinRows && aligned : force1 == 1);
+    };
+    const bool orA = one_read(runA, kmajA, m, A, lda), orB = one_read(runB, kmajB, n, B, ldb);
+    const size_t srA = runA && !kmajA && !orA ? L->mp : 0, srB = runB && !kmajB && !orB ? np : 0;  // padded row counts of the operands that need the pass
     const size_t room = (L->scratch_bytes - scale_fixed_bytes(L->mp, np)) / ub;
     ExtractOperand ea, eb;
     if (runA) {
         ea = ExtractOperand{kmajA, conjA, m, A, lda, (int8_t*)L->A_bound, bstrideA, L->sftA, s0A, g_batch.sa, nullptr, 1, L->mp};
+        ea.one_read = orA;
         if (srA) ea.amax = amax, ea.parts = amax_parts_for(m, k, room * srA / (srA + srB) / srA);
     }
     if (runB) {
         eb = ExtractOperand{kmajB, conjB, n, B, ldb, (int8_t*)L->B_bound, bstrideB, L->sftB, s0B, g_batch.sb, nullptr, 1, np};
+        eb.one_read = orB;
         if (srB) eb.amax = (char*)amax + (srA ? (size_t)ea.parts * srA * ub : 0), eb.parts = amax_parts_for(n, k, room * srB / (srA + srB) / srB);
     }
     if (srA + srB) OZ2_HIP(launch_amax_pair(stream, dtype, k, ea, eb));

@@ -83,9 +83,11 @@ struct ExtractOperand {
     void* amax = nullptr;      // row-strided operand: `parts` partial row-maxima arrays, pstride elements apart
     unsigned parts = 1;
     size_t pstride = 0;
+    bool one_read = false;     // row-strided operand: row maxima and bound plane from one read (no amax_pair_kernel pass, `amax` unused); needs extract_one_read_ok
 };
+bool extract_one_read_ok(int dtype, int backend, size_t kp);  // the one-read form exists: real types, INT8 planes, a single GEMM, kp <= 8192
 unsigned amax_parts_for(size_t rows, size_t k, size_t max_parts);
-hipError_t launch_amax_pair(hipStream_t stream, int dtype, size_t k, const ExtractOperand& A, const ExtractOperand& B);  // row-strided operands only
+hipError_t launch_amax_pair(hipStream_t stream, int dtype, size_t k, const ExtractOperand& A, const ExtractOperand& B);  // row-strided operands that keep the row-maxima pass (not one_read)
 hipError_t launch_extract_pair(hipStream_t stream, int dtype, int backend, size_t k, size_t kp, const ExtractOperand& A, const ExtractOperand& B, void* zero_p,
                                size_t zero_bytes);
 hipError_t launch_shift_finalize(hipStream_t stream, int backend, unsigned N, size_t rowsA, const int* maxA, int16_t* sftA, size_t rowsB,

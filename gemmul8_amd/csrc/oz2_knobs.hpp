@@ -18,6 +18,7 @@ struct Knobs {
     int crt_panels = 0;            // GEMMUL8_CRT_PANELS=<P>[r]: real INT8 whole call as P column panels, gemm(p) crt(p) back to back (SURVEY 8 f3 by cache residency); suffix r: every panel's residues go to panel 0's columns of C_mid (0: one GEMM launch, one CRT launch)
     int crt_panels_ring = 0;
     int scale_fold = 1;            // GEMMUL8_SCALE_FOLD=0: accurate mode's zero-fill, two extracts and shift finalize as launches of their own (9 launches) instead of the extract-pair launch that also zero-fills and the quantise launch that also finalizes (6)
+    int bounds_one_read = -1;      // GEMMUL8_BOUNDS_ONE_READ=0|1: accurate mode's bound plane of a row-strided operand after a row-maxima pass (0) / from one read of the operand wherever that form exists (1) (-1: by row count)
     int map_colblock = -1;         // GEMMUL8_MAP_COLBLOCK=<w>: tile-columns per column block of the GEMM tile walk, 0 = full width (-1: map_colblock's rule)
 };
 const Knobs& knobs();  // oz2_driver.hip

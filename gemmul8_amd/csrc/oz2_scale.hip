@@ -14,6 +14,7 @@
 // thread owns 4 consecutive k and emits one dword per plane (the reference's char4 granularity),
 // num_moduli is a run-time loop bound (no per-N template instantiation).
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -752,6 +753,176 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
     }
 }
 
+// Row-strided operand, MODE_BOUND, INT8 planes, real types: the bound plane from ONE read of the operand (no row-maxima pass before it).  One workgroup owns
+// a panel of TR rows over all of k and walks its 128-wide k tiles in order, the raw loads of OZ2_PANEL_DEPTH tiles in flight.  A row's shift is only known after
+// its last tile, so tile t is written with the PROVISIONAL shift s_t = 5 - ilogb0(maximum of the row over tiles 0 .. t) >= s0, and
+//     ceil(ceil(y 2^d) / 2^d) = ceil(y)   (real y >= 0, integer d >= 0)
+// turns a byte written with s_t = s0 + d into the byte of s0 exactly: a' = (a'' + 2^d - 1) >> d.  After the last tile the workgroup re-reads from the PLANE
+// (an eighth of the operand's bytes, its own stores of a moment ago) the tiles of its rows that were written before a larger binade appeared, and nothing
+// where every tile already held the row's top binade.  The steps E_t - E_(t-1) of the running exponent are kept per (row, tile) as one byte in LDS.
+// (int)ceil(ldexp(|x|, s0)) departs from the real-number value only where ldexp is inexact or the maximum is not finite: rows with s0 + (smallest exponent of
+// a nonzero element) < -1022 (a lower bound of that exponent is enough: a subnormal counts as 2^-1074) or with an infinite maximum are recomputed from a second
+// read of the row with the final s0 -- by the code of the two-pass form, so that every byte and every shift is the two-pass form's for all inputs.
+constexpr int kPanelMaxTiles = 64;  // k tiles per row of the step table (kp <= 8192); a longer k keeps the two-pass form (extract_one_read_ok)
+#ifndef OZ2_PANEL_DEPTH
+#define OZ2_PANEL_DEPTH 4  // tiles whose raw loads are in flight (16 registers each); 2 / 3 / 4 measured: DESIGN.md 3.4
+#endif
+template <typename T> __device__ __forceinline__ void stage_panel_body(const StageArgs& a, const unsigned bid) {
+    static_assert(!ET<T>::cplx, "real operands");
+    constexpr int TR = StageTile<T>::TR, TK = StageTile<T>::TK;
+    constexpr int CH = TK / 4, RPP = 256 / CH, NP = TR / RPP;  // 4-wide k chunks per row, rows per pass, passes: thread (pass, threadIdx.x) owns the same (row, chunk) in every tile
+    constexpr int RPL = 16 / (int)sizeof(T), RP = TR / RPL, KY = 256 / RP, NL = TK / KY;  // the load mapping of stage_strided_body
+    constexpr int D = OZ2_PANEL_DEPTH;
+    constexpr int kNone = INT_MIN;  // exponent of "no nonzero element yet"
+    constexpr int PITCH = TK + 16 / (int)sizeof(T);  // rows stay 16-B aligned
+    __shared__ __attribute__((aligned(16))) T tile[TR][PITCH];  // (a tile of its own: the strided body's array stays what every other kernel has)
+    __shared__ unsigned char step[TR][kPanelMaxTiles];
+    const unsigned nkt = (unsigned)(a.kp / TK);
+    const size_t r0 = (size_t)bid * TR;
+    const int rp = threadIdx.x % RP, ky = threadIdx.x / RP;
+    const size_t lrow = r0 + RPL * rp;
+    const T* X = (const T*)((const char*)a.X + OZ2_ZX);
+    const T* x = X + lrow;
+    const bool pair_ok = lrow + RPL - 1 < a.rows && ((reinterpret_cast<uintptr_t>(x) | (a.ld * sizeof(T))) & 15u) == 0;
+    typedef unsigned V4 __attribute__((ext_vector_type(4)));
+    const int c = threadIdx.x % CH, rg = threadIdx.x / CH;
+    int ex[NP];                         // running exponent of the row maximum (every lane of the row's 32 holds it); NaN never wins, Inf is INT_MAX
+    [[maybe_unused]] unsigned mnk[NP];  // this lane's smallest high word of a nonzero |x| (double)
+#pragma unroll
+    for (int p = 0; p < NP; ++p) ex[p] = kNone, mnk[p] = 0xFFFFFFFFu;
+    // Pipelined walk (a condition uniform over the workgroup): every row of the panel exists and every 16-byte row group is aligned -- the loads of a tile that
+    // lies inside k are then UNCONDITIONAL.  A load under a per-lane condition is merged with its other arm in the destination registers, and the compiler then waits for all
+    // loads in flight (vmcnt(0)) before every such merge: no pipeline at all.  The k tail and ragged / unaligned panels take the guarded loads.
+    const unsigned nfull = (unsigned)(a.k / TK);
+    auto fetch_guarded = [&](unsigned t, V4 (&b)[NL]) {
+#pragma unroll
+        for (int it = 0; it < NL; ++it) {
+            const size_t kg = (size_t)t * TK + ky + KY * it;
+            V4 v = {0u, 0u, 0u, 0u};
+            if (kg < a.k) {
+                if (pair_ok) {
+                    v = __builtin_nontemporal_load((const V4*)(x + kg * a.ld));
+                } else {
+#pragma unroll
+                    for (int e = 0; e < RPL; ++e) {
+                        const T q = (lrow + e < a.rows) ? x[kg * a.ld + e] : (T)0;
+                        __builtin_memcpy((char*)&v + e * sizeof(T), &q, sizeof(T));
+                    }
+                }
+            }
+            b[it] = v;
+        }
+    };
+    auto to_lds = [&](const V4 (&b)[NL]) {
+#pragma unroll
+        for (int it = 0; it < NL; ++it) {
+            const int kk = ky + KY * it;
+#pragma unroll
+            for (int e = 0; e < RPL; ++e) __builtin_memcpy(&tile[RPL * rp + e][kk], (const char*)&b[it] + e * sizeof(T), sizeof(T));
+        }
+    };
+    // tile t is in LDS: running exponents, the step table, the provisional bytes
+    auto consume = [&]<bool FAST>(unsigned t) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int rl = p * RPP + rg;
+            T v[4];
+            T lm = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = tile[rl][c * 4 + e];
+                const T ax = sizeof(T) == 8 ? (T)fabs((double)v[e]) : (T)fabsf((float)v[e]);
+                lm = ax > lm ? ax : lm;
+                if constexpr (sizeof(T) == 8) {
+                    const unsigned hw = (unsigned)__double2hiint((double)ax);
+                    mnk[p] = (v[e] != (T)0 && hw < mnk[p]) ? hw : mnk[p];
+                }
+            }
+            int key = lm == (T)0 ? kNone : lm == (T)INFINITY ? INT_MAX : ilogb0(lm);
+#pragma unroll
+            for (int off = CH / 2; off > 0; off >>= 1) key = max(key, __shfl_xor(key, off));
+            const int prev = ex[p];
+            ex[p] = max(prev, key);
+            if (c == 0) step[rl][t] = (unsigned char)(prev == kNone ? 0 : min(min(ex[p], 4096) - min(prev, 4096), 255));
+            if (FAST || r0 + rl < a.rows) emit4<T, MODE_BOUND>(a, r0 + rl, (size_t)t * TK + c * 4, v, ex[p] == kNone ? 5 : 5 - min(ex[p], 4096));
+        }
+    };
+    unsigned tdone = 0;  // tiles consumed by the pipelined loop
+    if (r0 + TR <= a.rows && ((reinterpret_cast<uintptr_t>(X + r0) | (a.ld * sizeof(T))) & 15u) == 0) {
+        auto fetch = [&](unsigned t, V4 (&b)[NL]) {
+#pragma unroll
+            for (int it = 0; it < NL; ++it) b[it] = __builtin_nontemporal_load((const V4*)(x + ((size_t)t * TK + ky + KY * it) * a.ld));
+        };
+        V4 buf[D][NL];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+#pragma unroll
+            for (int it = 0; it < NL; ++it) buf[j][it] = V4{0u, 0u, 0u, 0u};
+            if ((unsigned)j < nfull) fetch((unsigned)j, buf[j]);
+        }
+        for (unsigned t0 = 0; t0 < nfull; t0 += D) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const unsigned t = t0 + j;
+                if (t < nfull) {  // (uniform)
+                    to_lds(buf[j]);
+                    if (t + D < nfull) fetch(t + D, buf[j]);
+                    __syncthreads();
+                    consume.template operator()<true>(t);
+                    __syncthreads();
+                }
+            }
+        }
+        tdone = nfull;
+    }
+    // the k tail (a partial tile, the zero tiles up to kp) and every tile of a ragged or unaligned panel: guarded loads, one tile at a time
+    for (unsigned t = tdone; t < nkt; ++t) {
+        V4 b[NL];
+        fetch_guarded(t, b);
+        to_lds(b);
+        __syncthreads();
+        consume.template operator()<false>(t);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int rl = p * RPP + rg;
+        const size_t row = r0 + rl;
+        if (row >= a.rows) continue;
+        const int s0 = ex[p] == kNone ? 5 : ex[p] == INT_MAX ? 5 - ilogb0((T)INFINITY) : 5 - ex[p];  // = 5 - ilogb0(row maximum): ilogb is monotone
+        if (c == 0) {
+            ((int16_t*)((char*)a.sft0 + OZ2_ZW))[row] = (int16_t)s0;
+            if (a.sft0_keep) ((int16_t*)((char*)a.sft0_keep + OZ2_ZW))[row] = (int16_t)s0;
+        }
+        bool hazard = ex[p] == INT_MAX;
+        if constexpr (sizeof(T) == 8) {
+            unsigned mk = mnk[p];
+#pragma unroll
+            for (int off = CH / 2; off > 0; off >>= 1) mk = min(mk, (unsigned)__shfl_xor((int)mk, off));
+            const int emin = (mk >> 20) == 0 ? -1074 : (int)(mk >> 20) - 1023;  // a lower bound; NaN / Inf words never lower it
+            hazard = hazard || (ex[p] != kNone && mk != 0xFFFFFFFFu && s0 + emin < -1022);
+        }
+        if (hazard) {  // (uniform over the row's 32 lanes)
+            for (unsigned t = 0; t < nkt; ++t) {
+                const size_t k0 = (size_t)t * TK + c * 4;
+                T v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = (k0 + e < a.k) ? X[(k0 + e) * a.ld + row] : (T)0;
+                emit4<T, MODE_BOUND>(a, row, k0, v, s0);
+            }
+            continue;
+        }
+        unsigned d = 0;  // s_t - s0 of tile t - 1
+        for (int t = (int)nkt - 1; t >= 1; --t) {
+            d = min(d + step[rl][t], 64u);
+            if (d == 0) continue;
+            unsigned* q = (unsigned*)(a.lo + OZ2_ZW + row * a.kp + (size_t)(t - 1) * TK + c * 4);
+            const unsigned w = *q;  // four bytes <= 64 each: the per-byte sums below stay below 256
+            *q = d >= 8 ? (((w + 0x7F7F7F7Fu) >> 7) & 0x01010101u) : (((w + ((1u << d) - 1u) * 0x01010101u) >> d) & ((0xFFu >> d) * 0x01010101u));
+        }
+    }
+}
+
 // accurate-mode extract (MODE_BOUND) of BOTH operands in one launch (round 6; workgroups [0, nA) work on a, the rest on b; either share may be empty).  The
 // row maxima of row-strided operands come from amax_pair_kernel's partial arrays (no atomics, hence nothing to zero for them); the zero-fill of the bound GEMM's
 // maxima arrays rides on this launch (zero_p / zero_words of `a`).
@@ -767,6 +938,23 @@ template <typename T> __global__ void __launch_bounds__(256) extract_pair_kernel
         if (kmB) stage_kmajor_body<T, MODE_BOUND>(b, blockIdx.x - nA);
         else stage_strided_body<T, MODE_BOUND>(b, blockIdx.x - nA);
     }
+}
+// The same launch when an operand takes the one-read form (real types).  Operand form (fA / fB): 0 = row-strided after amax_pair_kernel, 1 = K-major,
+// 2 = row-strided from one read (stage_panel_body).  A kernel of its own: the panel body's registers (4 instead of 5 workgroups per CU) would otherwise be
+// paid by every call of extract_pair_kernel, also where no operand takes the form (1024^3, launch-bound: +0.9 us measured with one kernel for both).
+enum { FORM_STRIDED = 0, FORM_KMAJOR = 1, FORM_PANEL = 2 };
+template <typename T> __device__ __forceinline__ void extract_body(const StageArgs& a, const unsigned bid, const int form) {
+    if (form == FORM_KMAJOR) return stage_kmajor_body<T, MODE_BOUND>(a, bid);
+    if (form == FORM_PANEL) return stage_panel_body<T>(a, bid);
+    stage_strided_body<T, MODE_BOUND>(a, bid);
+}
+template <typename T> __global__ void __launch_bounds__(256) extract_panel_pair_kernel(const StageArgs a, const StageArgs b, const unsigned nA, const int fA, const int fB) {
+    if (a.zero_words) {
+        unsigned* zp = (unsigned*)((char*)a.zero_p + OZ2_ZW);
+        for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < a.zero_words; i += gridDim.x * 256u) zp[i] = 0u;
+    }
+    if (blockIdx.x < nA) extract_body<T>(a, blockIdx.x, fA);
+    else extract_body<T>(b, blockIdx.x - nA, fB);
 }
 // quantise (MODE_MOD) of BOTH operands in one launch: workgroups [0, nA) work on a, the rest on b; either share may be empty (skip-scaling,
 // single-operand callers).  The two halves are independent and at launch-bound sizes each of them is a ~5-10 us dispatch (1024^3: 12.7 + 9.5 us,
@@ -1136,7 +1324,7 @@ static StageArgs extract_args(int backend, size_t k, size_t kp, const ExtractOpe
 template <typename T> static hipError_t launch_amax_pair_t(hipStream_t stream, size_t k, const ExtractOperand& A, const ExtractOperand& B) {
     auto mk = [](const ExtractOperand& o) {
         AmaxOperand q{};
-        if (o.rows && !o.kmajor) q = AmaxOperand{o.X, o.ld, o.rows, o.xstride, o.amax, o.pstride, o.parts, (unsigned)((o.rows + 63) / 64)};
+        if (o.rows && !o.kmajor && !o.one_read) q = AmaxOperand{o.X, o.ld, o.rows, o.xstride, o.amax, o.pstride, o.parts, (unsigned)((o.rows + 63) / 64)};
         return q;
     };
     const AmaxOperand a = mk(A), b = mk(B);
@@ -1155,23 +1343,40 @@ hipError_t launch_amax_pair(hipStream_t stream, int dtype, size_t k, const Extra
     }
     return hipErrorInvalidValue;
 }
-template <typename T> static hipError_t launch_extract_pair_t(hipStream_t stream, bool kmA, StageArgs a, bool kmB, const StageArgs& b, void* zero_p, size_t zero_bytes) {
-    const size_t nA = stage_blocks<T, MODE_BOUND>(kmA, a), nB = stage_blocks<T, MODE_BOUND>(kmB, b);
+template <typename T> static size_t extract_blocks(int form, const StageArgs& a) {
+    if (form == FORM_PANEL) return (a.rows + StageTile<T>::TR - 1) / StageTile<T>::TR;  // one workgroup per row panel
+    return stage_blocks<T, MODE_BOUND>(form == FORM_KMAJOR, a);
+}
+template <typename T> static hipError_t launch_extract_pair_t(hipStream_t stream, int kmA, StageArgs a, int kmB, const StageArgs& b, void* zero_p, size_t zero_bytes) {
+    const size_t nA = extract_blocks<T>(kmA, a), nB = extract_blocks<T>(kmB, b);
     if (nA + nB == 0) return zero_bytes ? launch_zero(stream, zero_p, zero_bytes) : hipSuccess;
     if (nA + nB > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     if (zero_p && zero_bytes) a.zero_p = (unsigned*)zero_p, a.zero_words = (unsigned)(zero_bytes / 4);
-    hipLaunchKernelGGL(extract_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
+    if constexpr (!ET<T>::cplx) {
+        if (kmA == FORM_PANEL || kmB == FORM_PANEL) {
+            hipLaunchKernelGGL(extract_panel_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, kmA, kmB);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL(extract_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, kmA, kmB);
     return hipGetLastError();
+}
+// where the one-read panel body (stage_panel_body) exists: real types, INT8 planes, a single GEMM, k within the step table
+bool extract_one_read_ok(int dtype, int backend, size_t kp) {
+    return (dtype == kF32 || dtype == kF64) && backend == kINT8 && g_batch.batch == 1 && kp / StageTile<double>::TK <= (size_t)kPanelMaxTiles;
 }
 // extract of both operands (rows == 0: absent) in ONE launch; zero_p / zero_bytes: words the launch also zero-fills (the bound GEMM's maxima arrays)
 hipError_t launch_extract_pair(hipStream_t stream, int dtype, int backend, size_t k, size_t kp, const ExtractOperand& A, const ExtractOperand& B, void* zero_p,
                                size_t zero_bytes) {
     const StageArgs a = extract_args(backend, k, kp, A), b = extract_args(backend, k, kp, B);
+    auto form = [&](const ExtractOperand& o) { return o.kmajor ? FORM_KMAJOR : o.one_read ? FORM_PANEL : FORM_STRIDED; };
+    if ((A.one_read || B.one_read) && !extract_one_read_ok(dtype, backend, kp)) return hipErrorInvalidValue;
+    const int fA = form(A), fB = form(B);
     switch (dtype) {
-    case kF32: return launch_extract_pair_t<float>(stream, A.kmajor, a, B.kmajor, b, zero_p, zero_bytes);
-    case kF64: return launch_extract_pair_t<double>(stream, A.kmajor, a, B.kmajor, b, zero_p, zero_bytes);
-    case kC32: return launch_extract_pair_t<float2>(stream, A.kmajor, a, B.kmajor, b, zero_p, zero_bytes);
-    case kC64: return launch_extract_pair_t<double2>(stream, A.kmajor, a, B.kmajor, b, zero_p, zero_bytes);
+    case kF32: return launch_extract_pair_t<float>(stream, fA, a, fB, b, zero_p, zero_bytes);
+    case kF64: return launch_extract_pair_t<double>(stream, fA, a, fB, b, zero_p, zero_bytes);
+    case kC32: return launch_extract_pair_t<float2>(stream, fA, a, fB, b, zero_p, zero_bytes);
+    case kC64: return launch_extract_pair_t<double2>(stream, fA, a, fB, b, zero_p, zero_bytes);
     }
     return hipErrorInvalidValue;
 }
