@@ -36,7 +36,7 @@ _lib = None
 
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
            "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
-           "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk"]
+           "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk", "gemmul8_syr2k"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
 
@@ -124,6 +124,9 @@ def bind(L):
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
     L.gemmul8_herk.restype = C.c_int
     L.gemmul8_herk.argtypes = L.gemmul8_syrk.argtypes
+    L.gemmul8_syr2k.restype = C.c_int
+    L.gemmul8_syr2k.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
     L.gemmul8_set_fp8_bound_mode.restype = C.c_int
     L.gemmul8_set_fp8_bound_mode.argtypes = [C.c_int]
     L.gemmul8_set_nonfinite_mode.restype = C.c_int
@@ -263,6 +266,41 @@ def herk(A, num_moduli, uplo="L", trans="N", fastmode=False, alpha=1.0, beta=0.0
     rc = lib().gemmul8_herk(st, _dtype_code(dt), INT8, UPLO[uplo], OPS[trans], n, k, al.ctypes.data, A.data_ptr(), lda, be.ctypes.data,
                             C_out.data_ptr(), C_out.shape[1], num_moduli, int(fastmode), work.data_ptr(), tm)
     check(rc, "gemmul8_herk")
+    return C_out, (list(tm) if timers else None), work
+
+
+def syr2k_work_size(is_complex, n, k, num_moduli):
+    """Bytes of workspace gemmul8_syr2k needs: that of the equivalent GEMM, whose inner dimension is twice k rounded up to a multiple of 256."""
+    return work_size(is_complex, INT8, n, n, 2 * ((k + 255) // 256 * 256), num_moduli)[0]
+
+
+def syr2k(A, B, num_moduli, uplo="L", trans="N", fastmode=False, alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, timers=False):
+    """One triangle of C = alpha*(A*B^T + B*A^T) + beta*C (trans "N", A and B are n x k) or alpha*(A^T*B + B^T*A) + beta*C (trans "T", A and B are
+    k x n; plain transpose for complex types too) through gemmul8_syr2k: INT8 backend, the triangle `uplo` ("L" / "U", diagonal included) bit-identical
+    to `gemm(P, Q, opA=trans, opB="T" if trans == "N" else "N")` with P = [A, Z, B, Z], Q = [B, Z, A, Z] along k (Z: zeros up to a multiple of 256), the
+    other strict triangle of C_out neither read nor written.  A, B and C_out are column-major matrices held as tensors of shape (cols, rows), as in `gemm`;
+    A and B may have different leading dimensions (pass views through `lda` = tensor.stride(0)) or be the same tensor; a fresh C_out is zero-filled.
+    Returns (C, timers_ns or None, work)."""
+    import numpy as np
+    import torch
+    dt = A.dtype
+    for X in (A, B):
+        assert X.is_cuda and X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]
+    if B.dtype != dt or B.shape != A.shape or (C_out is not None and (C_out.dtype != dt or C_out.dim() != 2 or C_out.stride(1) != 1)):
+        raise TypeError("A, B and C_out must share one dtype, A and B one shape, and every column must be contiguous")
+    n, k = (A.shape[1], A.shape[0]) if trans == "N" else (A.shape[0], A.shape[1])
+    if C_out is None:
+        C_out = torch.zeros((n, n), dtype=dt, device=A.device)
+    if work is None:
+        work = torch.empty(syr2k_work_size(dt.is_complex, n, k, num_moduli), dtype=torch.uint8, device=A.device)
+    np_dt = {torch.float32: np.float32, torch.float64: np.float64, torch.complex64: np.complex64, torch.complex128: np.complex128}[dt]
+    al = np.array([alpha], dtype=np_dt)
+    be = np.array([beta], dtype=np_dt)
+    tm = (C.c_double * 4)() if timers else None
+    st = stream if stream is not None else torch.cuda.current_stream(A.device).cuda_stream
+    rc = lib().gemmul8_syr2k(st, _dtype_code(dt), INT8, UPLO[uplo], OPS[trans], n, k, al.ctypes.data, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0),
+                             be.ctypes.data, C_out.data_ptr(), C_out.stride(0), num_moduli, int(fastmode), work.data_ptr(), tm)
+    check(rc, "gemmul8_syr2k")
     return C_out, (list(tm) if timers else None), work
 
 

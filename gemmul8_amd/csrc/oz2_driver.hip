@@ -229,6 +229,30 @@ static int scale_scratch(const gemmul8_layout* L, size_t n, int** rowmax, int** 
     return GEMMUL8_OK;
 }
 
+// the accurate mode's bound GEMM on INT8 bound planes: the maxima of |op(A)| |op(B)| over ncols columns of B's planes, atomicMax into rowmax / colmax
+static int bound_gemm_i8(hipStream_t stream, bool cplx, const gemmul8_layout* L, size_t m, size_t ncols, const int8_t* Ab, const int8_t* Bb, int* rowmax, int* colmax) {
+    if (!cplx) {
+        const int8_t* As[1] = {Ab};
+        const int8_t* Bs[1] = {Bb};
+        OZ2_HIP(launch_gemm_i8_max(stream, 1, As, Bs, L->kp, m, ncols, rowmax, colmax));
+    } else {
+        // bound planes: 0 = |Re|, 1 = |Im|, 2 = |Re|-|Im| (scaling_accu_complex.hpp:441-460, find_max.hpp:99-114):
+        //   C1 = ArBi + AiBr (K-concatenation of two products), C1 + C0 = ArBr + AiBi with C0 = (Ar-Ai)(Br-Bi);
+        //   the maxima of both matrices accumulate into the same rowmax/colmax.
+        const int8_t* As[3] = {Ab, Ab + L->sizeA, Ab + 2 * L->sizeA};
+        const int8_t* Bs[3] = {Bb + L->sizeB, Bb, Bb + 2 * L->sizeB};
+        //   One launch over the three segments; the maxima are taken after the second (C1) and after the third (C1 + C0).
+        const bool two_launches = knobs().cplx_bound_launches == 2;  // A/B and testing switch (oz2_knobs.hpp)
+        if (two_launches) {
+            OZ2_HIP(launch_gemm_i8_max(stream, 2, As, Bs, L->kp, m, ncols, rowmax, colmax));
+            OZ2_HIP(launch_gemm_i8_max(stream, 3, As, Bs, L->kp, m, ncols, rowmax, colmax));
+        } else {
+            OZ2_HIP(launch_gemm_i8_max(stream, 3, As, Bs, L->kp, m, ncols, rowmax, colmax, 2));
+        }
+    }
+    return GEMMUL8_OK;
+}
+
 // nf: non-finite mode 1 (gemmul8_set_nonfinite_mode) -- passed down from the whole-call entry points only; the phase-level entry points run mode 0
 // rows from which a row-strided operand takes the one-read extract (16 / 32 rows per workgroup): measured, DESIGN.md 3.4
 constexpr size_t kOneReadMinRows = 8192;
@@ -312,24 +336,8 @@ static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int 
             OZ2_HIP(launch_gemm_f8_bound_cplx(stream, 2, Ab + L->sizeA, Bb, L->kp, k, m, ncols, fbuf, L->mp, rowmax, colmax + col_begin));
             OZ2_HIP(launch_gemm_f8_bound_cplx(stream, 3, Ab + 2 * L->sizeA, Bb + 2 * L->sizeB, L->kp, k, m, ncols, fbuf, L->mp, rowmax,
                                               colmax + col_begin));
-        } else if (!cplx) {
-            const int8_t* As[1] = {Ab};
-            const int8_t* Bs[1] = {Bb};
-            OZ2_HIP(launch_gemm_i8_max(stream, 1, As, Bs, L->kp, m, col_end - col_begin, rowmax, colmax + col_begin));
         } else {
-            // bound planes: 0 = |Re|, 1 = |Im|, 2 = |Re|-|Im| (scaling_accu_complex.hpp:441-460, find_max.hpp:99-114):
-            //   C1 = ArBi + AiBr (K-concatenation of two products), C1 + C0 = ArBr + AiBi with C0 = (Ar-Ai)(Br-Bi);
-            //   the maxima of both matrices accumulate into the same rowmax/colmax.
-            const int8_t* As[3] = {Ab, Ab + L->sizeA, Ab + 2 * L->sizeA};
-            const int8_t* Bs[3] = {Bb + L->sizeB, Bb, Bb + 2 * L->sizeB};
-            //   One launch over the three segments; the maxima are taken after the second (C1) and after the third (C1 + C0).
-            const bool two_launches = knobs().cplx_bound_launches == 2;  // A/B and testing switch (oz2_knobs.hpp)
-            if (two_launches) {
-                OZ2_HIP(launch_gemm_i8_max(stream, 2, As, Bs, L->kp, m, col_end - col_begin, rowmax, colmax + col_begin));
-                OZ2_HIP(launch_gemm_i8_max(stream, 3, As, Bs, L->kp, m, col_end - col_begin, rowmax, colmax + col_begin));
-            } else {
-                OZ2_HIP(launch_gemm_i8_max(stream, 3, As, Bs, L->kp, m, col_end - col_begin, rowmax, colmax + col_begin, 2));
-            }
+            if (int rc2 = bound_gemm_i8(stream, cplx, L, m, col_end - col_begin, Ab, Bb, rowmax, colmax + col_begin)) return rc2;
         }
     }
     return GEMMUL8_OK;
@@ -679,8 +687,53 @@ int gemmul8_gemm(void* stream_, int dtype, int backend, int op_A, int op_B, size
 // the right-hand Re planes are A_lo's).  Left panels come from A_lo, right panels from (A_lo part 0, B_lo parts 1, 2); the combine Cr = X - Y,
 // Ci = Z - X - Y does not change.  Im C is NOT bitwise antisymmetric (the CRT's mod-P reduction is not odd): every stored entry is computed as the
 // GEMM computes that entry, never mirrored.  The CRT's Hermitian arm takes real scalars and stores +0.0 as the diagonal's imaginary part.
-static int rank_k(bool herm, hipStream_t stream, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A,
-                  size_t lda, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+//
+// ---- symmetric rank-2k update (kSyr2k; B != nullptr).  A B^T + B A^T = P Q^T with P = [A | Z | B], Q = [B | Z | A], Z = the zero columns that bring k to
+// kh = padding256(k): ONE GEMM (trans, trans == N ? T : N) with the inner dimension 2 kh, in whose workspace layout the call works.  Row i of P and row i of Q
+// hold the same elements, so the two sides share their shifts (sftB = sftA; the fast mode's round-up sums are taken in P's order) and the bound product is
+// symmetric, but Q's planes are P's with the K halves swapped: genuinely distinct arrays.  syr2k_scale fills both from one read of A and one of B per phase
+// (the SEG2 kernels of oz2_scale.hip); everything behind the scaling is SYRK's, with B's planes as the right-hand panels
+// (tests/test_syr2k_premise.py pins the premise on the oracle).
+enum RankKind { kSyrk = 0, kHerk = 1, kSyr2k = 2 };
+static int syr2k_scale(hipStream_t stream, int dtype, bool kmaj, size_t n, size_t k, const void* A, size_t lda, const void* B, size_t ldb, unsigned N, int fastmode,
+                       const gemmul8_layout& L) {
+    const bool cplx = is_complex(dtype);
+    const size_t kh = L.kp / 2, np = padding256(n);
+    QuantOperand oa{kmaj, false, n, A, lda, L.sftA, (int8_t*)L.A_lo, L.sizeA, L.part_strideA};
+    const Seg2Planes lo{B, ldb, (int8_t*)L.B_lo, L.sizeB, L.part_strideB};
+    if (fastmode) {
+        OZ2_HIP(launch_fast_shift_seg2(stream, dtype, N, k, oa, lo));
+    } else {
+        int *rowmax, *colmax;
+        void* amax;
+        int16_t *s0A, *s0B;
+        if (int rc = scale_scratch(&L, n, &rowmax, &colmax, &amax, &s0A, &s0B)) return rc;
+        ExtractOperand ea{kmaj, false, n, A, lda, (int8_t*)L.A_bound, cplx ? L.sizeA : 0, L.sftA, s0A, 0, nullptr, 1, L.mp};
+        if (!kmaj) {  // row maxima: A's and B's partial arrays side by side, one maximum per row over all of them (not the one-read extract: the bits are the same)
+            const size_t ub = is_f32(dtype) ? 4 : 8;
+            const size_t room = (L.scratch_bytes - scale_fixed_bytes(L.mp, np)) / ub;
+            ExtractOperand eb = ea;
+            ea.amax = amax, ea.parts = eb.parts = amax_parts_for(n, k, room / (2 * L.mp));
+            eb.X = B, eb.ld = ldb, eb.amax = (char*)amax + (size_t)ea.parts * L.mp * ub;
+            OZ2_HIP(launch_amax_pair(stream, dtype, k, ea, eb));
+            ea.parts *= 2;
+        }
+        const Seg2Planes bound{B, ldb, (int8_t*)L.B_bound, 0, cplx ? L.sizeB : 0};
+        OZ2_HIP(launch_extract_seg2(stream, dtype, k, kh, ea, bound, rowmax, 4 * (L.mp + np)));
+        if (int rc = bound_gemm_i8(stream, cplx, &L, n, n, (const int8_t*)L.A_bound, (const int8_t*)L.B_bound, rowmax, colmax)) return rc;  // the full square
+        if (knobs().scale_fold) {  // rowmax == colmax and one preliminary shift per row: one finalize, folded into the quantise launch
+            oa.fin_sft0 = s0A, oa.fin_max = rowmax, oa.fin_log2P = GEMMUL8_LOG2P_INT8[N - 2];
+        } else {
+            OZ2_HIP(launch_shift_finalize(stream, kINT8, N, n, rowmax, L.sftA, 0, colmax, L.sftB));
+        }
+    }
+    OZ2_HIP(launch_quantise_seg2(stream, dtype, 0, (int)N, k, kh, oa, lo));
+    return GEMMUL8_OK;
+}
+
+static int rank_k(int kind, hipStream_t stream, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A,
+                  size_t lda, const void* B, size_t ldb, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    const bool herm = kind == kHerk;
     if (timers_ns) timers_ns[0] = timers_ns[1] = timers_ns[2] = timers_ns[3] = 0.0;
     if (dtype < 0 || dtype > 3 || backend < 0 || backend > 1) return GEMMUL8_E_ARG;
     if (herm && !is_complex(dtype)) return GEMMUL8_E_ARG;  // BLAS has no real HERK
@@ -689,43 +742,49 @@ static int rank_k(bool herm, hipStream_t stream, int dtype, int backend, int upl
     trans = norm_op(trans);
     if ((uplo != GEMMUL8_LOWER && uplo != GEMMUL8_UPPER) || (trans != 0 && trans != (herm ? 2 : 1))) return GEMMUL8_E_ARG;
     if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
-    if (!alpha || !beta || !A || !C || !work) return GEMMUL8_E_ARG;
-    if (k > (size_t(1) << 17)) return GEMMUL8_E_ARG;
+    if (!alpha || !beta || !A || !C || !work || (kind == kSyr2k && !B)) return GEMMUL8_E_ARG;
+    if (k > (size_t(1) << (kind == kSyr2k ? 16 : 17))) return GEMMUL8_E_ARG;  // (syr2k: the equivalent GEMM's inner dimension is 2 padding256(k))
     if (backend == kFP8) return GEMMUL8_E_UNSUPPORTED;  // the FP6 panel images of A and B differ in layout: B's planes are not A's
     if (n == 0 || k == 0) return GEMMUL8_OK;
     const bool cplx = is_complex(dtype);
     gemmul8_layout L;
-    int rc = gemmul8_get_layout(dtype, backend, n, n, k, N, work, nullptr, nullptr, 0, 0, &L);
+    int rc = gemmul8_get_layout(dtype, backend, n, n, kind == kSyr2k ? 2 * padding256(k) : k, N, work, nullptr, nullptr, 0, 0, &L);
     if (rc) return rc;
-    const TwinPlanes twin{(int8_t*)L.B_lo, L.sizeB, L.part_strideB};  // herm: the equivalent GEMM's B planes (rows unpadded), parts 1 and 2
-    L.B_lo = L.A_lo, L.B_bound = L.A_bound, L.sftB = L.sftA, L.sizeB = L.sizeA, L.part_strideB = L.part_strideA;
+    const TwinPlanes twin{(int8_t*)L.B_lo, L.sizeB, L.part_strideB};  // herm, syr2k: the equivalent GEMM's B planes (rows unpadded); herm: parts 1 and 2 only
+    if (kind == kSyr2k) L.sftB = L.sftA;
+    else L.B_lo = L.A_lo, L.B_bound = L.A_bound, L.sftB = L.sftA, L.sizeB = L.sizeA, L.part_strideB = L.part_strideA;
     Timer* T = timers_ns ? thread_timer() : nullptr;
     if (T && hipEventRecord(T->ev[0], stream) != hipSuccess) {
         (void)hipGetLastError();
         T = nullptr;
     }
     const int op_A = trans, op_B = trans == 0 ? (herm ? 2 : 1) : 0;
-    rc = scale_nf(stream, dtype, backend, op_A, op_B, n, n, k, A, lda, A, lda, N, fastmode, 0, N, &L, 0, 1, false, herm ? &twin : nullptr);
+    if (kind == kSyr2k) rc = syr2k_scale(stream, dtype, trans != 0, n, k, A, lda, B, ldb, N, fastmode, L);
+    else rc = scale_nf(stream, dtype, backend, op_A, op_B, n, n, k, A, lda, A, lda, N, fastmode, 0, N, &L, 0, 1, false, herm ? &twin : nullptr);
     if (rc) return rc;
     if (T) OZ2_HIP(hipEventRecord(T->ev[1], stream));
     const int tri = uplo == GEMMUL8_LOWER ? 1 : 2;
     const int8_t* A_lo = (const int8_t*)L.A_lo;
+    const bool own = kind != kSyrk;  // the right-hand panels are planes of their own (herm: but for plane set 0)
     if (!cplx) {
-        OZ2_HIP(launch_gemm_i8_mod(stream, A_lo, A_lo, L.sizeA, L.sizeA, L.kp, n, n, 0, (int)N, (int8_t*)L.C_mid, L.mp, L.sizeC, true, tri));
+        OZ2_HIP(launch_gemm_i8_mod(stream, A_lo, kind == kSyr2k ? twin.lo : A_lo, L.sizeA, kind == kSyr2k ? twin.plane_stride : L.sizeA, L.kp, n, n, 0, (int)N,
+                                   (int8_t*)L.C_mid, L.mp, L.sizeC, true, tri));
     } else {  // X = ArAr^T, Y = AiAi^T, Z = (Ar+Ai)(Ar+Ai)^T as in gemmul8_lowprec_gemm, each over the triangle's tiles (herm: the right factors are Ar, -Ai, Ar-Ai)
         const size_t per_mod = 2 * L.sizeC;
         size_t chunk = L.scratch_bytes / per_mod;
         if (chunk == 0) return GEMMUL8_E_ARG;
         if (const size_t want = (size_t)knobs().cplx_chunk; want >= 1 && want < chunk) chunk = want;
         int8_t* rx = (int8_t*)L.scratch;
-        const size_t strideR = herm ? twin.plane_stride : L.sizeA;  // the right-hand Im and Re + Im planes
+        const size_t strideR = own ? twin.plane_stride : L.sizeA;  // the right-hand Im and Re + Im planes ...
+        const size_t strideR0 = kind == kSyr2k ? twin.plane_stride : L.sizeA;  // ... and Re planes
         for (unsigned t0 = 0; t0 < N; t0 += (unsigned)chunk) {
             const unsigned t1 = std::min<unsigned>(N, t0 + (unsigned)chunk);
             int8_t* ry = rx + (size_t)(t1 - t0) * L.sizeC;
             const int8_t *Ar = A_lo + (size_t)t0 * L.sizeA, *Ai = Ar + L.part_strideA, *As = Ar + 2 * L.part_strideA;
-            const int8_t* Bi = herm ? twin.lo + twin.part_stride + (size_t)t0 * twin.plane_stride : Ai;
-            const int8_t* Bs = herm ? twin.lo + 2 * twin.part_stride + (size_t)t0 * twin.plane_stride : As;
-            OZ2_HIP(launch_gemm_i8_mod(stream, Ar, Ar, L.sizeA, L.sizeA, L.kp, n, n, (int)t0, (int)t1, rx, L.mp, L.sizeC, false, tri));
+            const int8_t* Br = kind == kSyr2k ? twin.lo + (size_t)t0 * twin.plane_stride : Ar;
+            const int8_t* Bi = own ? twin.lo + twin.part_stride + (size_t)t0 * twin.plane_stride : Ai;
+            const int8_t* Bs = own ? twin.lo + 2 * twin.part_stride + (size_t)t0 * twin.plane_stride : As;
+            OZ2_HIP(launch_gemm_i8_mod(stream, Ar, Br, L.sizeA, strideR0, L.kp, n, n, (int)t0, (int)t1, rx, L.mp, L.sizeC, false, tri));
             OZ2_HIP(launch_gemm_i8_mod(stream, Ai, Bi, L.sizeA, strideR, L.kp, n, n, (int)t0, (int)t1, ry, L.mp, L.sizeC, false, tri));
             OZ2_HIP(launch_gemm_i8_cplx(stream, As, Bs, L.sizeA, strideR, L.kp, n, n, (int)t0, (int)t1, rx, ry, L.sizeC,
                                         (int8_t*)L.C_mid + (size_t)t0 * 2 * L.sizeC, L.mp, 2 * L.sizeC, tri));
@@ -749,12 +808,17 @@ static int rank_k(bool herm, hipStream_t stream, int dtype, int backend, int upl
 
 int gemmul8_syrk(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda,
                  const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
-    return rank_k(false, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, beta, C, ldc, N, fastmode, work, timers_ns);
+    return rank_k(kSyrk, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, nullptr, 0, beta, C, ldc, N, fastmode, work, timers_ns);
 }
 
 int gemmul8_herk(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda,
                  const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
-    return rank_k(true, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, beta, C, ldc, N, fastmode, work, timers_ns);
+    return rank_k(kHerk, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, nullptr, 0, beta, C, ldc, N, fastmode, work, timers_ns);
+}
+
+int gemmul8_syr2k(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda, const void* B,
+                  size_t ldb, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    return rank_k(kSyr2k, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, B, ldb, beta, C, ldc, N, fastmode, work, timers_ns);
 }
 
 int gemmul8_add_f64(void* stream_, double* dst, const double* src, size_t count) {

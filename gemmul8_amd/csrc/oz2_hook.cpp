@@ -11,6 +11,7 @@
 //   hipblas{S,D,C,Z}gemmStridedBatched, hipblasGemmStridedBatchedEx         yes (torch.bmm): no early out, degenerate calls are the native routine's
 //   hipblas{S,D,C,Z}syrk(_64), hipblas{C,Z}herk(_64)                        yes: one triangle through gemmul8_syrk / gemmul8_herk (INT8 backend, k <= 2^17; HERK: real
 //                                                                             alpha / beta, N / C only); everything else is the native routine's, see try_syrk_impl
+//   hipblas{S,D,C,Z}syr2k(_64)                                              yes: one triangle through gemmul8_syr2k (INT8 backend, k <= 2^16, N / T only); see try_syrk_impl
 //   hipblasLtMatmul, hipblasLtDestroy                                       yes (PyTorch's float32 matmuls): the plain case only, see lt_try
 //   hipblasLtMatrixLayoutCreate / SetAttribute / Destroy                    yes: record what a layout holds (hipBLASLt cannot be asked)
 //   rocblas_{s,d,c,z}gemm, rocblas_{s,d,c,z}gemm_strided_batched,           yes, only with GEMMUL8_HOOK_ROCBLAS=1: applications that call rocBLAS directly
@@ -37,7 +38,7 @@
 //   GEMMUL8_HOOK_ROCBLAS           per call    "1" = the rocBLAS entry points above act
 //   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
 //   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call);
-//                                              a second line for hipblas{S,D,C,Z}syrk and a third for hipblas{C,Z}herk when one was seen
+//                                              a line each for hipblas{S,D,C,Z}syrk, hipblas{C,Z}herk and hipblas{S,D,C,Z}syr2k when one was seen
 //   GEMMUL8_HOOK_VERBOSE           per call    "1" = say why a hipblasLtMatmul call was left to the native routine
 //
 // Per-handle state under a mutex: three grow-only stream-ordered buffers (hipMallocAsync / hipFreeAsync), event hand-off when the handle's
@@ -64,12 +65,13 @@
 
 // The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
 // `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
-// then stays 0 -- and no gemmul8_syrk / gemmul8_herk: every SYRK / HERK call then goes to the native routine); the shim, which binds to this
+// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k: every SYRK / HERK / SYR2K call then goes to the native routine); the shim, which binds to this
 // project's own libgemmul8.so, requires every entry.
 #define OZ2_ABI(X)                                                                                          \
     X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
     X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
-    X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak))) X(herk, __attribute__((weak)))
+    X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak))) X(herk, __attribute__((weak))) \
+    X(syr2k, __attribute__((weak)))
 #ifndef OZ2_HOOK_SHIM
 #define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
 OZ2_ABI(X)
@@ -542,11 +544,13 @@ struct NativeScope {
     NativeScope(const NativeScope&) = delete;
     NativeScope& operator=(const NativeScope&) = delete;
 };
+enum { kSYRK = 0, kHERK = 1, kSYR2K = 2 };  // the rank-k routines of try_syrk
+const char* const kRankName[3] = {"SYRK", "HERK", "SYR2K"};
 struct HookStats {
     std::atomic<unsigned long long> emu_calls{0}, nat_calls{0};
     std::atomic<unsigned long long> emu_mflops{0}, nat_mflops{0};  // 2 m n k batch / 1e6 (x 4 for complex), rounded down
-    // hipblas?syrk [0] / hipblas?herk [1]: n (n + 1) k / 1e6 (x 4)
-    std::atomic<unsigned long long> emu_syrk[2] = {{0}, {0}}, nat_syrk[2] = {{0}, {0}}, emu_syrk_mflops[2] = {{0}, {0}}, nat_syrk_mflops[2] = {{0}, {0}};
+    // hipblas?syrk [0] / hipblas?herk [1] / hipblas?syr2k [2]: n (n + 1) k / 1e6 (x 4; syr2k: x 2)
+    std::atomic<unsigned long long> emu_syrk[3] = {{0}, {0}, {0}}, nat_syrk[3] = {{0}, {0}, {0}}, emu_syrk_mflops[3] = {{0}, {0}, {0}}, nat_syrk_mflops[3] = {{0}, {0}, {0}};
     static void dump();
     HookStats() { std::atexit(&HookStats::dump); }
 };
@@ -559,11 +563,11 @@ void HookStats::dump() {
     HookStats& h = hook_stats();
     std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu GEMM calls (%.3f TFLOP), native %llu GEMM calls through the hooked entry points (%.3f TFLOP)\n",
                  h.emu_calls.load(), h.emu_mflops.load() * 1e-6, h.nat_calls.load(), h.nat_mflops.load() * 1e-6);
-    for (int herm = 0; herm < 2; ++herm)
-        if (h.emu_syrk[herm].load() + h.nat_syrk[herm].load())
+    for (int kind = 0; kind < 3; ++kind)
+        if (h.emu_syrk[kind].load() + h.nat_syrk[kind].load())
             std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu %s calls (%.3f TFLOP), native %llu %s calls through the hooked entry points (%.3f TFLOP)\n",
-                         h.emu_syrk[herm].load(), herm ? "HERK" : "SYRK", h.emu_syrk_mflops[herm].load() * 1e-6, h.nat_syrk[herm].load(),
-                         herm ? "HERK" : "SYRK", h.nat_syrk_mflops[herm].load() * 1e-6);
+                         h.emu_syrk[kind].load(), kRankName[kind], h.emu_syrk_mflops[kind].load() * 1e-6, h.nat_syrk[kind].load(), kRankName[kind],
+                         h.nat_syrk_mflops[kind].load() * 1e-6);
 }
 void count_call(bool emulated, const GemmCall& c) {
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
@@ -596,7 +600,8 @@ bool floor_model_declines(int dtype, double m, double n, double k, unsigned N, b
 }
 // quiet = a query (gemmul8_hook_would_emulate), not a call: no log line.  syrk = 1: a SYRK call, 2: a HERK call (m == n): a number is a floor on
 // n (n + 1) k, `auto` takes the GEMM model's decision for (n, n, k) -- native and emulated SYRK / HERK are both about half their GEMMs; no scan of
-// either has been fitted.
+// either has been fitted.  syrk = 3: a SYR2K call: a number is a floor on 2 n (n + 1) k; the caller passes 2 k, so that `auto` takes the GEMM model's
+// decision for (n, n, 2 k) -- no SYR2K scan has been fitted either.
 bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch = 1.0, bool quiet = false, int syrk = 0) {
     const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
     if (!s || !*s) return false;  // the reference's behaviour: every selected call is emulated
@@ -606,14 +611,14 @@ bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast,
         declined = floor_model_declines(dtype, m, n, k, N, fast, backend, batch);
     } else {
         const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
-        declined = f && (syrk ? n * (n + 1.0) * k : 2.0 * m * n * k) < (double)f;
+        declined = f && (syrk ? n * (n + 1.0) * k : 2.0 * m * n * k) < (double)f;  // (SYR2K: k is 2 k here)
     }
     if (declined && !quiet) {
-        static std::once_flag told[3];  // GEMM, SYRK, HERK
+        static std::once_flag told[4];  // GEMM, SYRK, HERK, SYR2K
         std::call_once(told[syrk], [&] {
             if (syrk)
                 std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %c%s n = %.0f, k = %.0f (%u moduli) stays on the native routine -- calls below the "
-                                     "floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], syrk == 2 ? "HERK" : "SYRK", n, k, N);
+                                     "floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], kRankName[syrk - 1], n, syrk == 3 ? 0.5 * k : k, N);
             else
                 std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cGEMM %.0f x %.0f x %.0f (batch %.0f, %u moduli%s) stays on the native routine -- "
                                      "calls below the floor are NOT emulated (this message is printed once)\n",
@@ -719,43 +724,49 @@ bool try_emulate(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* sta
 // Selection: the type's GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, k > 2^17, a moduli count outside
 // the type's range (each said once per routine), a fill mode or operation other than upper / lower and N / T (HERK: N / C), a dimension an int cannot
 // hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: below_floor's SYRK / HERK form.  GEMMUL8_DIST and the skip-scaling switches do not apply.
-bool try_syrk_impl(bool herm, hipblasHandle_t handle, int dtype, int uplo, int trans, int n, int k, const void* alpha, const void* A, int lda,
-                   const void* beta, void* C, int ldc, hipblasStatus_t* status) {
-    const auto syrk = herm ? abi().herk : abi().syrk;  // (one signature)
-    if (!syrk) return false;
-    const char* const name = herm ? "HERK" : "SYRK";
+// hipblas{S,D,C,Z}syr2k (kind = kSYR2K; B != nullptr): one triangle of alpha (A B^T + B A^T) + beta C through gemmul8_syr2k -- the same selection, with
+// k <= 2^16 (the equivalent GEMM's inner dimension is 2 pad256(k)), that GEMM's workspace, and below_floor's SYR2K form.
+bool try_syrk_impl(int kind, hipblasHandle_t handle, int dtype, int uplo, int trans, int n, int k, const void* alpha, const void* A, int lda, const void* B,
+                   int ldb, const void* beta, void* C, int ldc, hipblasStatus_t* status) {
+    const bool herm = kind == kHERK, two = kind == kSYR2K;
+    if (!(two ? (bool)abi().syr2k : herm ? (bool)abi().herk : (bool)abi().syrk)) return false;
+    const char* const name = kRankName[kind];
+    const int max_k = two ? kMaxK / 2 : kMaxK;
     if ((uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) || (trans != HIPBLAS_OP_N && trans != (herm ? HIPBLAS_OP_C : HIPBLAS_OP_T)))
         return false;
     Selection s;
     if (!selection_from_env(dtype, &s)) {
         if (s.N != 0) {
-            static std::once_flag told[2];
-            std::call_once(told[herm], [&] {
+            static std::once_flag told[3];
+            std::call_once(told[kind], [&] {
                 std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %c%s calls use the native routine\n", kTypes[dtype].nmod, s.N,
                              kTypes[dtype].max_moduli, "SDCZ"[dtype], name);
             });
         }
         return false;
     }
-    if (s.backend == GEMMUL8_FP8 || k > kMaxK) {
-        static std::once_flag told[2][2];  // the backend, the k range: one notice each
-        std::call_once(told[herm][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
+    if (s.backend == GEMMUL8_FP8 || k > max_k) {
+        static std::once_flag told[3][2];  // the backend, the k range: one notice each
+        std::call_once(told[kind][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
             std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for k <= %d only (GEMMUL8_BACKEND=%d, k=%d): using the native routine "
-                                 "for such calls\n", name, kMaxK, s.backend, k);
+                                 "for such calls\n", name, max_k, s.backend, k);
         });
         return false;
     }
-    if (below_floor(dtype, (double)n, (double)n, (double)k, s.N, s.fast, s.backend, 1.0, false, herm ? 2 : 1)) return false;
+    if (below_floor(dtype, (double)n, (double)n, (two ? 2.0 : 1.0) * (double)k, s.N, s.fast, s.backend, 1.0, false, kind + 1)) return false;
     LockedState l = lock_ordered(handle, nullptr);
     if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
-    const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)n, (size_t)n, (size_t)k, s.N, 0, 0, nullptr, nullptr);
-    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, herm ? "workC (herk)" : "workC (syrk)"); st != HIPBLAS_STATUS_SUCCESS)
-        return *status = st, true;
-    const int rc = syrk(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, beta, C, (size_t)ldc, s.N, s.fast,
-                        l.sp->wC.ptr, nullptr);
+    const size_t kw = two ? 2 * (((size_t)k + 255) / 256 * 256) : (size_t)k;  // the inner dimension of the GEMM whose workspace the call needs
+    const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)n, (size_t)n, kw, s.N, 0, 0, nullptr, nullptr);
+    static const char* const what[3] = {"workC (syrk)", "workC (herk)", "workC (syr2k)"};
+    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, what[kind]); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
+    const int rc = two ? abi().syr2k(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, B, (size_t)ldb, beta, C, (size_t)ldc,
+                                     s.N, s.fast, l.sp->wC.ptr, nullptr)
+                       : (herm ? abi().herk : abi().syrk)(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, beta, C,
+                                                          (size_t)ldc, s.N, s.fast, l.sp->wC.ptr, nullptr);
     if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
-        static std::once_flag warned[2];
-        std::call_once(warned[herm], [&] {
+        static std::once_flag warned[3];
+        std::call_once(warned[kind], [&] {
             std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a %s call (status %d; type %d, n=%d k=%d): using the native routine for such calls\n", name,
                          rc, dtype, n, k);
         });
@@ -765,18 +776,19 @@ bool try_syrk_impl(bool herm, hipblasHandle_t handle, int dtype, int uplo, int t
 }
 // counted front end; false = the native routine takes the call: also an empty product, a null pointer (the native routine reports it) or a
 // dimension an int cannot hold
-bool try_syrk(bool herm, hipblasHandle_t handle, int dtype, int uplo, int trans, int64_t n, int64_t k, const void* alpha, const void* A, int64_t lda,
-              const void* beta, void* C, int64_t ldc, hipblasStatus_t* status) {
+bool try_syrk(int kind, hipblasHandle_t handle, int dtype, int uplo, int trans, int64_t n, int64_t k, const void* alpha, const void* A, int64_t lda,
+              const void* B, int64_t ldb, const void* beta, void* C, int64_t ldc, hipblasStatus_t* status) {
     if (tl_native_depth > 0) return false;
     const int64_t lim = 2147483647;
     if (n <= 0 || k <= 0 || !alpha || !beta || !A || !C || n > lim || k > lim || lda > lim || ldc > lim) return false;
-    const bool served = try_syrk_impl(herm, handle, dtype, uplo, trans, (int)n, (int)k, alpha, A, (int)lda, beta, C, (int)ldc, status);
+    if (kind == kSYR2K && (!B || ldb > lim)) return false;
+    const bool served = try_syrk_impl(kind, handle, dtype, uplo, trans, (int)n, (int)k, alpha, A, (int)lda, B, (int)ldb, beta, C, (int)ldc, status);
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
     if (on) {
         HookStats& h = hook_stats();
-        const unsigned long long mf = (unsigned long long)((double)n * ((double)n + 1.0) * (double)k * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
-        (served ? h.emu_syrk : h.nat_syrk)[herm].fetch_add(1, std::memory_order_relaxed);
-        (served ? h.emu_syrk_mflops : h.nat_syrk_mflops)[herm].fetch_add(mf, std::memory_order_relaxed);
+        const unsigned long long mf = (unsigned long long)((double)n * ((double)n + 1.0) * (double)k * (dtype >= 2 ? 4.0 : 1.0) * (kind == kSYR2K ? 2.0 : 1.0) * 1e-6);
+        (served ? h.emu_syrk : h.nat_syrk)[kind].fetch_add(1, std::memory_order_relaxed);
+        (served ? h.emu_syrk_mflops : h.nat_syrk_mflops)[kind].fetch_add(mf, std::memory_order_relaxed);
     }
     return served;
 }
@@ -1217,15 +1229,22 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
                          I lda, const T* beta, T* C, I ldc) {                                                                           \
         hipblasStatus_t st;                                                                                                             \
-        if (try_syrk(false, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, beta, C, ldc, &st)) return st;                   \
+        if (try_syrk(kSYRK, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, nullptr, 0, beta, C, ldc, &st)) return st;       \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, beta, C, ldc);                      \
+    }
+#define OZ2_SYR2K_HOOK(NAME, T, I, CODE)                                                                                                \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
+                         I lda, const T* B, I ldb, const T* beta, T* C, I ldc) {                                                        \
+        hipblasStatus_t st;                                                                                                             \
+        if (try_syrk(kSYR2K, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;          \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc);              \
     }
 // hipblas{C,Z}herk: R = the real type of alpha and beta
 #define OZ2_HERK_HOOK(NAME, T, R, I, CODE)                                                                                              \
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const R* alpha, const T* A, \
                          I lda, const R* beta, T* C, I ldc) {                                                                           \
         hipblasStatus_t st;                                                                                                             \
-        if (try_syrk(true, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, beta, C, ldc, &st)) return st;                    \
+        if (try_syrk(kHERK, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, nullptr, 0, beta, C, ldc, &st)) return st;       \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, beta, C, ldc);                      \
     }
 // one stamp per type; Z / ZZ: the substitution indices of the mangled names, which differ between the real and the complex forms
@@ -1235,6 +1254,8 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     OZ2_SB_HOOK(hipblas##U##gemmStridedBatched, T, CODE)                                                                                \
     OZ2_SYRK_HOOK(hipblas##U##syrk, T, int, CODE)                                                                                       \
     OZ2_SYRK_HOOK(hipblas##U##syrk_64, T, int64_t, CODE)                                                                                \
+    OZ2_SYR2K_HOOK(hipblas##U##syr2k, T, int, CODE)                                                                                     \
+    OZ2_SYR2K_HOOK(hipblas##U##syr2k_64, T, int64_t, CODE)                                                                              \
     OZ2_ROCBLAS_HOOK(rocblas_##L##gemm, rocblas_##L##gemm_strided_batched, T, CODE)                                                     \
     OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_##L##_32, T, int, CODE,                                                                        \
                          "_Z30rocblas_internal_gemm_templateI" TAG "E15rocblas_status_P15_rocblas_handle18rocblas_operation_" Z         \
@@ -1259,6 +1280,7 @@ OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
 #undef OZ2_ROCBLAS_HOOK
 #undef OZ2_GEMM_EX_HOOK
 #undef OZ2_HERK_HOOK
+#undef OZ2_SYR2K_HOOK
 #undef OZ2_SYRK_HOOK
 #undef OZ2_SB_HOOK
 #undef OZ2_GEMM_HOOK

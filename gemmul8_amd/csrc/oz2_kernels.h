@@ -122,6 +122,21 @@ hipError_t launch_fast_shift_pair(hipStream_t stream, int dtype, int backend, un
 hipError_t launch_quantise_pair(hipStream_t stream, int dtype, int backend, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A,
                                 const QuantOperand& B);
 
+// ---- gemmul8_syr2k: the operand is the K-concatenation [A.X | S.X2] of two matrices of one form (A.kmajor) with A.rows rows, each k long and zero-filled
+// to kp = padding256(k).  INT8 planes, mode 0, a single GEMM.  Plane rows are 2 kp bytes apart; an element of X goes to columns [0, kp) of A.lo and, the
+// same bytes, to columns [kp, 2 kp) of S.lo2; an element of X2 the other way round: the planes of [X | X2] and of [X2 | X] from one read of X and of X2.
+struct Seg2Planes {
+    const void* X2 = nullptr;
+    size_t ld2 = 0;
+    int8_t* lo2 = nullptr;
+    size_t plane_stride2 = 0, part_stride2 = 0;
+};
+// one shift per row of the concatenation, to A.sft: every lane runs its loop over X's row, then X2's -- the plain form's order on the materialised rows
+hipError_t launch_fast_shift_seg2(hipStream_t stream, int dtype, unsigned N, size_t k, const QuantOperand& A, const Seg2Planes& S);
+// row-strided operands: A.amax holds the partial row maxima of BOTH matrices (launch_amax_pair on (X, X2), A.parts arrays in all); K-major: in the kernel
+hipError_t launch_extract_seg2(hipStream_t stream, int dtype, size_t k, size_t kp, const ExtractOperand& A, const Seg2Planes& S, void* zero_p, size_t zero_bytes);
+hipError_t launch_quantise_seg2(hipStream_t stream, int dtype, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A, const Seg2Planes& S);
+
 // ---- non-finite mode 1 (gemmul8_set_nonfinite_mode; oz2_nonfinite.hip)
 // the shift of a flagged row of op(A) / column of op(B) (one holding a NaN or an Inf): no mode-0 shift comes near it (a few thousand at most),
 // and the CRT's scalbn(R, sftA[i] + sftB[j]) of the finite R is +-0 with it

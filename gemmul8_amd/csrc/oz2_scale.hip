@@ -162,6 +162,12 @@ struct StageArgs {
     // of Re - Im of the SAME loaded elements -- go to parts 1 and 2 of a second plane array with strides of its own (its part 0 is not written)
     int8_t* lo2;
     size_t plane_stride2, part_stride2;
+    // SEG2 kernels (gemmul8_syr2k; INT8 planes): the operand is the K-concatenation [X | X2] of two matrices of the same form, each k long and zero-filled
+    // to kp (a multiple of 256: the seam).  Plane rows are `pitch` = 2 kp bytes apart; an element of segment s at k0 goes to column s kp + k0 of `lo` and,
+    // the same bytes, to column (1 - s) kp + k0 of `lo2` (plane_stride2 / part_stride2): the planes of [X | X2] and of [X2 | X] from one read of each
+    const void* X2;
+    size_t ld2;
+    size_t pitch;
 };
 // item blockIdx.z of a batched launch: every workspace pointer moves by bw, the operand by bx (both 0 for a single GEMM).  The offsets
 // are applied at the few points of use: a modified COPY of the argument block lands in scratch memory (the quantise kernels ran 6x
@@ -333,7 +339,8 @@ template <bool WIDE> __device__ __forceinline__ int residue_from_small(int Ri, f
 // TWIN (quantise_twin_kernel): out2 = the element's place in the twin's planes.  The twin's chain is the one a.conj selects, run on -xi: trunc, rint and the
 // exact fma are odd functions under round-to-nearest, so its level-1 remainder is -I to the bit and only the level-2 quotient (whose magic-number sum rounds
 // ties to even, and whose even-p tie is one-sided) is run again, on (-Ri, -Fi) -- the bytes a second pass over the operand with the other `conj` would write.
-template <typename T, bool TWIN = false> __device__ __forceinline__ void emit4_mod_float(const StageArgs& a, int8_t* out, [[maybe_unused]] int8_t* out2, const T (&v)[4], int s) {
+// SEG2 (the syr2k kernels): out2 = the element's place in the second plane array, which gets the SAME bytes, all three plane sets of a complex type.
+template <typename T, bool TWIN = false, bool SEG2 = false> __device__ __forceinline__ void emit4_mod_float(const StageArgs& a, int8_t* out, [[maybe_unused]] int8_t* out2, const T (&v)[4], int s) {
     using E = ET<T>;
     double xr[4], xi[4];
     bool big = false;
@@ -433,12 +440,20 @@ template <typename T, bool TWIN = false> __device__ __forceinline__ void emit4_m
                             *(unsigned*)(o2 + 2 * a.part_stride2) = pack(rd);
                         }
                     }
+                    if constexpr (SEG2) {
+                        int8_t* o2 = out2 + (size_t)tt * a.plane_stride2;
+                        *(unsigned*)o2 = pack(rr);
+                        if constexpr (E::cplx) {
+                            *(unsigned*)(o2 + a.part_stride2) = pack(ri);
+                            *(unsigned*)(o2 + 2 * a.part_stride2) = pack(rs);
+                        }
+                    }
                 }
             }
         }
     };
     const bool anybig = __any(big);
-    if constexpr (TWIN) {  // INT8 planes only
+    if constexpr (TWIN || SEG2) {  // INT8 planes only
         if (anybig) run.template operator()<false, true>();
         else run.template operator()<false, false>();
         return;
@@ -452,9 +467,35 @@ template <typename T, bool TWIN = false> __device__ __forceinline__ void emit4_m
     }
 }
 
-template <typename T, int MODE, bool TWIN = false>
-__device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0, const T (&vin)[4], int s) {
+template <typename T, int MODE, bool TWIN = false, bool SEG2 = false>
+__device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0, const T (&vin)[4], int s, [[maybe_unused]] unsigned seg = 0) {
     using E = ET<T>;
+    if constexpr (SEG2) {  // INT8 planes at a pitch, written twice (k0: inside segment `seg`)
+        int8_t* const o1 = a.lo + OZ2_ZW + row * a.pitch + (seg ? a.kp : 0) + k0;
+        int8_t* const o2 = a.lo2 + OZ2_ZW + row * a.pitch + (seg ? 0 : a.kp) + k0;
+        if constexpr (MODE == MODE_BOUND) {
+            unsigned wr = 0, wi = 0, wd = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {  // the INT8 bound bytes of the plain form below
+                auto ub = [&](double x) { return (int)ceil(ldexp(fabs(x), s)); };
+                const int br = ub(E::re(vin[e]));
+                wr |= ((unsigned)br & 0xFFu) << (8 * e);
+                if constexpr (E::cplx) {
+                    const int bi = ub(E::im(vin[e]));
+                    wi |= ((unsigned)bi & 0xFFu) << (8 * e);
+                    wd |= ((unsigned)(br - bi) & 0xFFu) << (8 * e);
+                }
+            }
+            *(unsigned*)o1 = wr, *(unsigned*)o2 = wr;
+            if constexpr (E::cplx) {
+                *(unsigned*)(o1 + a.part_stride) = wi, *(unsigned*)(o2 + a.part_stride2) = wi;
+                *(unsigned*)(o1 + 2 * a.part_stride) = wd, *(unsigned*)(o2 + 2 * a.part_stride2) = wd;
+            }
+        } else {
+            emit4_mod_float<T, false, true>(a, o1, o2, vin, s);
+        }
+        return;
+    }
     T v[4] = {vin[0], vin[1], vin[2], vin[3]};
     if (MODE == MODE_MOD && a.nf && s == kNonfiniteShift) {  // flagged row (non-finite mode 1): zero planes, the sentinel never reaches ldexp
 #pragma unroll
@@ -628,6 +669,75 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
     }
 }
 
+// K-major operand of the SEG2 kernels (StageArgs::X2): row r of [X | X2] is row r of X, then row r of X2.  MODE_BOUND: one workgroup per row, the row's
+// maximum over BOTH segments (one shift per row of the concatenation), then the bytes of both -- the two-pass form of stage_kmajor_body, the second pass
+// re-reading what the first left in the cache.  MODE_MOD: the workgroups of stage_kmajor_body per segment, segment 0's chunks of a row first; a chunk starts
+// at a multiple of 1024 inside its own segment, so none straddles the seam.
+template <typename T, int MODE> __device__ __forceinline__ void stage_kmajor_seg2_body(const StageArgs& a, const unsigned bid) {
+    using E = ET<T>;
+    using U = typename E::U;
+    const T* const X0 = (const T*)((const char*)a.X + OZ2_ZX);
+    const T* const X1 = (const T*)((const char*)a.X2 + OZ2_ZX);
+    if constexpr (MODE == MODE_MOD && sizeof(T) <= 8) {
+        const unsigned nch = (unsigned)(a.kp / 1024 + (a.kp % 1024 != 0));
+        const size_t row = bid / (2 * nch);
+        unsigned ch = bid - (unsigned)row * 2 * nch;
+        const unsigned seg = ch >= nch;
+        ch -= seg * nch;
+        const size_t k0 = (size_t)ch * 1024 + (size_t)threadIdx.x * 4;
+        if (k0 >= a.kp) return;
+        const T* x = seg ? X1 + row * a.ld2 : X0 + row * a.ld;
+        const int s = OZ2_ROW_SHIFT(a, row, seg == 0 && k0 == 0);
+        T v[4];
+        load4<T>(x, k0, a.k, v);
+        emit4<T, MODE, false, true>(a, row, k0, v, s, seg);
+    } else {
+        const size_t row = bid;
+        const T* const x0 = X0 + row * a.ld;
+        const T* const x1 = X1 + row * a.ld2;
+        int s;
+        if constexpr (MODE == MODE_BOUND) {
+            __shared__ U sm[4];
+            U am = 0;
+            for (unsigned seg = 0; seg < 2; ++seg) {
+                const T* x = seg ? x1 : x0;
+                for (size_t k0 = (size_t)threadIdx.x * 4; k0 < a.k; k0 += 1024) {
+                    T v[4];
+                    load4<T, false>(x, k0, a.k, v);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const U ar = (U)fabs(E::re(v[e])), ai = (U)fabs(E::im(v[e]));
+                        am = ar > am ? ar : am;
+                        am = ai > am ? ai : am;
+                    }
+                }
+            }
+            am = wave_max(am);
+            if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = am;
+            __syncthreads();
+            am = sm[0];
+            am = sm[1] > am ? sm[1] : am;
+            am = sm[2] > am ? sm[2] : am;
+            am = sm[3] > am ? sm[3] : am;
+            s = 5 - ilogb0(am);
+            if (threadIdx.x == 0) {
+                ((int16_t*)((char*)a.sft0 + OZ2_ZW))[row] = (int16_t)s;
+                if (a.sft0_keep) ((int16_t*)((char*)a.sft0_keep + OZ2_ZW))[row] = (int16_t)s;
+            }
+        } else {
+            s = OZ2_ROW_SHIFT(a, row, threadIdx.x == 0);
+        }
+        for (unsigned seg = 0; seg < 2; ++seg) {
+            const T* x = seg ? x1 : x0;
+            for (size_t k0 = (size_t)threadIdx.x * 4; k0 < a.kp; k0 += 1024) {
+                T v[4];
+                load4<T>(x, k0, a.k, v);
+                emit4<T, MODE, false, true>(a, row, k0, v, s, seg);
+            }
+        }
+    }
+}
+
 // Row-strided operand: 1-D grid of ceil(kp/TK) * ceil(rows/TR) workgroups, the row-tile index fastest (a 2-D grid would cap the
 // row-tile count at 65535, i.e. operands of ~1M rows); 256 threads; tile TR rows x TK k staged RAW in LDS
 template <typename T> struct StageTile {
@@ -640,7 +750,8 @@ template <typename T> struct StageTile {
     static constexpr int TR = sizeof(T) == 4 ? 32 : sizeof(T) == 16 ? 8 : OZ2_STAGE_TR8;
     static constexpr int TK = 128;
 };
-template <typename T, int MODE, bool TWIN = false>
+// SEG2 (the syr2k kernels): twice the k tiles, those of X first, then those of X2; the row maxima (MODE_BOUND) are those of both matrices' partial arrays
+template <typename T, int MODE, bool TWIN = false, bool SEG2 = false>
 __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const unsigned bid) {
     using E = ET<T>;
     using U = typename E::U;
@@ -656,7 +767,11 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
     const unsigned nrt = (unsigned)((a.rows + TR - 1) / TR);
     const unsigned kt = bid / nrt, rt = bid - kt * nrt;
     const size_t r0 = (size_t)rt * TR;
-    const size_t kb = (size_t)kt * TK;
+    [[maybe_unused]] unsigned seg = 0;
+    if constexpr (SEG2) seg = kt >= (unsigned)(a.kp / TK);
+    const size_t kb = (size_t)(kt - seg * (unsigned)(a.kp / TK)) * TK;  // (inside the segment)
+    const void* const Xs = SEG2 && seg ? a.X2 : a.X;
+    const size_t ld = SEG2 && seg ? a.ld2 : a.ld;
     if constexpr (MODE == MODE_BOUND) {
         // row maxima of the tile's rows = the maximum over the k splits' partial arrays (amax_pair_kernel): 256 threads = TR rows x PL lanes, one
         // load per lane and partial (non-negative IEEE patterns order like unsigned integers), published to the passes below by the tile's barrier
@@ -687,8 +802,8 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
         constexpr int KY = 256 / RP;     // k values fetched per pass
         const int rp = threadIdx.x % RP, ky = threadIdx.x / RP;
         const size_t row = r0 + RPL * rp;
-        const T* x = (const T*)((const char*)a.X + OZ2_ZX) + row;
-        const bool pair_ok = row + RPL - 1 < a.rows && ((reinterpret_cast<uintptr_t>(x) | (a.ld * sizeof(T))) & 15u) == 0;
+        const T* x = (const T*)((const char*)Xs + OZ2_ZX) + row;
+        const bool pair_ok = row + RPL - 1 < a.rows && ((reinterpret_cast<uintptr_t>(x) | (ld * sizeof(T))) & 15u) == 0;
         typedef unsigned V4 __attribute__((ext_vector_type(4)));
         V4 buf[TK / KY];
 #pragma unroll
@@ -697,11 +812,11 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
             V4 v = {0u, 0u, 0u, 0u};
             if (kg < a.k) {
                 if (pair_ok) {
-                    v = __builtin_nontemporal_load((const V4*)(x + kg * a.ld));
+                    v = __builtin_nontemporal_load((const V4*)(x + kg * ld));
                 } else {
 #pragma unroll
                     for (int e = 0; e < RPL; ++e) {
-                        const T t = (row + e < a.rows) ? x[kg * a.ld + e] : E::zero();
+                        const T t = (row + e < a.rows) ? x[kg * ld + e] : E::zero();
                         __builtin_memcpy((char*)&v + e * sizeof(T), &t, sizeof(T));
                     }
                 }
@@ -718,12 +833,12 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
         constexpr int KY = 256 / TR;  // k values fetched per pass
         const int rx = threadIdx.x % TR, ky = threadIdx.x / TR;
         const size_t row = r0 + rx;
-        const T* x = (const T*)((const char*)a.X + OZ2_ZX) + row;
+        const T* x = (const T*)((const char*)Xs + OZ2_ZX) + row;
 #pragma unroll 4
         for (int it = 0; it < TK / KY; ++it) {
             const int kk = ky + KY * it;
             const size_t kg = kb + kk;
-            tile[rx][kk] = (row < a.rows && kg < a.k) ? x[kg * a.ld] : E::zero();
+            tile[rx][kk] = (row < a.rows && kg < a.k) ? x[kg * ld] : E::zero();
         }
     }
     __syncthreads();
@@ -749,7 +864,7 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
         T v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = tile[rl][c * 4 + e];
-        emit4<T, MODE, TWIN>(a, row, kb + c * 4, v, s);
+        emit4<T, MODE, TWIN, SEG2>(a, row, kb + c * 4, v, s, seg);
     }
 }
 
@@ -975,6 +1090,21 @@ template <typename T> __global__ void __launch_bounds__(256) quantise_twin_kerne
     static_assert(ET<T>::cplx, "complex operands");
     if (km) stage_kmajor_body<T, MODE_MOD, true>(a, blockIdx.x);
     else stage_strided_body<T, MODE_MOD, true>(a, blockIdx.x);
+}
+// gemmul8_syr2k: ONE operand that is the K-concatenation of two matrices (StageArgs::X2), whose every loaded element leaves twice -- to the planes of
+// [X | X2] at a.lo and, K halves swapped, to those of [X2 | X] at a.lo2: both sides of X X2^T + X2 X^T from one read of X and one of X2.  Kernels of
+// their own, as the twin kernel is: extract_pair_kernel and quantise_pair_kernel keep their registers.
+template <typename T> __global__ void __launch_bounds__(256) extract_seg2_kernel(const StageArgs a, const int km) {
+    if (a.zero_words) {
+        unsigned* zp = (unsigned*)((char*)a.zero_p + OZ2_ZW);
+        for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < a.zero_words; i += gridDim.x * 256u) zp[i] = 0u;
+    }
+    if (km) stage_kmajor_seg2_body<T, MODE_BOUND>(a, blockIdx.x);
+    else stage_strided_body<T, MODE_BOUND, false, true>(a, blockIdx.x);
+}
+template <typename T> __global__ void __launch_bounds__(256) quantise_seg2_kernel(const StageArgs a, const int km) {
+    if (km) stage_kmajor_seg2_body<T, MODE_MOD>(a, blockIdx.x);
+    else stage_strided_body<T, MODE_MOD, false, true>(a, blockIdx.x);
 }
 static_assert(2 * sizeof(StageArgs) + 16 <= 4096, "two argument blocks must fit the 4 KiB kernel-argument segment");
 
@@ -1432,6 +1562,47 @@ static hipError_t launch_quantise_twin(hipStream_t stream, int dtype, int t_begi
     return hipGetLastError();
 }
 
+// ---- gemmul8_syr2k: the operand passes over [A.X | S.X2] (kp = the padded length of ONE segment; plane rows are 2 kp apart)
+template <typename T, int MODE> static size_t seg2_blocks(bool kmajor, const StageArgs& a) {
+    if (kmajor) return a.rows * ((MODE == MODE_MOD && sizeof(T) <= 8) ? 2 * ((a.kp + 1023) / 1024) : 1);
+    return 2 * (a.kp / StageTile<T>::TK) * ((a.rows + StageTile<T>::TR - 1) / StageTile<T>::TR);
+}
+static void seg2_args(StageArgs& a, size_t kp, const Seg2Planes& S) {
+    a.X2 = S.X2, a.ld2 = S.ld2, a.pitch = 2 * kp;
+    a.lo2 = S.lo2, a.plane_stride2 = S.plane_stride2, a.part_stride2 = S.part_stride2;
+}
+template <typename T, int MODE> static hipError_t launch_seg2_t(hipStream_t stream, bool kmajor, const StageArgs& a) {
+    const size_t nb = seg2_blocks<T, MODE>(kmajor, a);
+    if (nb == 0 || nb > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if constexpr (MODE == MODE_BOUND) hipLaunchKernelGGL(extract_seg2_kernel<T>, dim3((unsigned)nb), dim3(256), 0, stream, a, (int)kmajor);
+    else hipLaunchKernelGGL(quantise_seg2_kernel<T>, dim3((unsigned)nb), dim3(256), 0, stream, a, (int)kmajor);
+    return hipGetLastError();
+}
+template <int MODE> static hipError_t launch_seg2(hipStream_t stream, int dtype, bool kmajor, const StageArgs& a) {
+    if (g_batch.batch != 1 || a.rows == 0 || a.kp % 256 != 0 || !a.X2 || !a.lo2) return hipErrorInvalidValue;
+    switch (dtype) {
+    case kF32: return launch_seg2_t<float, MODE>(stream, kmajor, a);
+    case kF64: return launch_seg2_t<double, MODE>(stream, kmajor, a);
+    case kC32: return launch_seg2_t<float2, MODE>(stream, kmajor, a);
+    case kC64: return launch_seg2_t<double2, MODE>(stream, kmajor, a);
+    }
+    return hipErrorInvalidValue;
+}
+hipError_t launch_extract_seg2(hipStream_t stream, int dtype, size_t k, size_t kp, const ExtractOperand& A, const Seg2Planes& S, void* zero_p, size_t zero_bytes) {
+    if (A.one_read || A.conj) return hipErrorInvalidValue;
+    StageArgs a = extract_args(kINT8, k, kp, A);
+    seg2_args(a, kp, S);
+    if (zero_p && zero_bytes) a.zero_p = (unsigned*)zero_p, a.zero_words = (unsigned)(zero_bytes / 4);
+    return launch_seg2<MODE_BOUND>(stream, dtype, A.kmajor, a);
+}
+hipError_t launch_quantise_seg2(hipStream_t stream, int dtype, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A, const Seg2Planes& S) {
+    if (t_end <= t_begin) return hipSuccess;
+    if (A.conj || A.f6_rows || A.nf || A.lo2) return hipErrorInvalidValue;
+    StageArgs a = quantise_args(kINT8, t_begin, t_end, k, kp, A);
+    seg2_args(a, kp, S);
+    return launch_seg2<MODE_MOD>(stream, dtype, A.kmajor, a);
+}
+
 hipError_t launch_quantise_pair(hipStream_t stream, int dtype, int backend, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A,
                                 const QuantOperand& B) {
     if ((A.rows == 0 && B.rows == 0) || t_end <= t_begin) return hipSuccess;
@@ -1522,40 +1693,48 @@ __device__ __forceinline__ int fast_sft(float amax, float vecnrm, float log2P) {
 }
 
 // K-major: one 256-thread block per row (scaling_fast_real.hpp:142-164)
-template <typename T> __device__ __forceinline__ void fast_shift_kmajor_body(const T* X, size_t ld, size_t k, int16_t* sft, float log2P, const unsigned bid) {
+// SEG2 (gemmul8_syr2k): the row of the K-concatenation [X | Z | X2], Z = the zero columns that bring X's k to a multiple of 256: every lane keeps its
+// accumulators and runs its loop over X's row, then over X2's.  Element j of X2 sits in column pad256(k) + j of the concatenation, which is lane j % 256
+// again, and a zero leaves a round-up sum as it is: the order of the reduction is the one the plain form has on the materialised concatenation.
+template <typename T, bool SEG2 = false>
+__device__ __forceinline__ void fast_shift_kmajor_body(const T* X, size_t ld, size_t k, int16_t* sft, float log2P, const unsigned bid, [[maybe_unused]] const T* X2 = nullptr,
+                                                       [[maybe_unused]] size_t ld2 = 0) {
     using E = ET<T>;
     using U = typename E::U;
     __shared__ U samax[32], ssum[32];
-    const T* x = X + (size_t)bid * ld;
     U amax = 0, sum = 0;
-    size_t i = threadIdx.x;
-    for (; i + 3 * 256 < k; i += 4 * 256) {  // four loads ahead of their (sequential) round-up FMAs
-        T v[4];
+    auto segment = [&](const T* x) {
+        size_t i = threadIdx.x;
+        for (; i + 3 * 256 < k; i += 4 * 256) {  // four loads ahead of their (sequential) round-up FMAs
+            T v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = x[i + 256 * u];
+            for (int u = 0; u < 4; ++u) v[u] = x[i + 256 * u];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const U ar = (U)fabs(E::re(v[u]));
+            for (int u = 0; u < 4; ++u) {
+                const U ar = (U)fabs(E::re(v[u]));
+                amax = ar > amax ? ar : amax;
+                sum = sqr_add_ru<U>(ar, sum);
+                if constexpr (E::cplx) {
+                    const U ai = (U)fabs(E::im(v[u]));
+                    amax = ai > amax ? ai : amax;
+                    sum = sqr_add_ru<U>(ai, sum);
+                }
+            }
+        }
+        for (; i < k; i += 256) {
+            const T v = x[i];
+            const U ar = (U)fabs(E::re(v));
             amax = ar > amax ? ar : amax;
             sum = sqr_add_ru<U>(ar, sum);
             if constexpr (E::cplx) {
-                const U ai = (U)fabs(E::im(v[u]));
+                const U ai = (U)fabs(E::im(v));
                 amax = ai > amax ? ai : amax;
                 sum = sqr_add_ru<U>(ai, sum);
             }
         }
-    }
-    for (; i < k; i += 256) {
-        const T v = x[i];
-        const U ar = (U)fabs(E::re(v));
-        amax = ar > amax ? ar : amax;
-        sum = sqr_add_ru<U>(ar, sum);
-        if constexpr (E::cplx) {
-            const U ai = (U)fabs(E::im(v));
-            amax = ai > amax ? ai : amax;
-            sum = sqr_add_ru<U>(ai, sum);
-        }
-    }
+    };
+    segment(X + (size_t)bid * ld);
+    if constexpr (SEG2) segment(X2 + (size_t)bid * ld2);
     amax = tree32_max(amax);
     sum = tree32_sum_ru(sum);
     if ((threadIdx.x & 31) == 0) {
@@ -1578,7 +1757,10 @@ template <typename T> __device__ __forceinline__ void fast_shift_kmajor_body(con
 // = one 128-byte line per column -- 512 workgroups for 8192 rows of doubles where the 32 x 32 form had 256 and 8-byte loads.  The loads of
 // eight chain steps are issued ahead of their round-up FMAs: the chain itself is sequential, and with one load per step it ran at one
 // memory latency per element (289 us for 1024 x 16384 doubles; 128 MiB).
-template <typename T> __device__ __forceinline__ void fast_shift_strided_body(const T* X, size_t ld, size_t rows, size_t k, int16_t* sft, float log2P, const unsigned bid) {
+// SEG2: as above -- lane ty of a row takes columns ty, ty + 32, ... of X, then of X2 (pad256(k) is a multiple of 32).
+template <typename T, bool SEG2 = false>
+__device__ __forceinline__ void fast_shift_strided_body(const T* X, size_t ld, size_t rows, size_t k, int16_t* sft, float log2P, const unsigned bid,
+                                                        [[maybe_unused]] const T* X2 = nullptr, [[maybe_unused]] size_t ld2 = 0) {
     using E = ET<T>;
     using U = typename E::U;
     constexpr int RPL = 16 / (int)sizeof(T), RPB = 8 * RPL;
@@ -1598,57 +1780,61 @@ template <typename T> __device__ __forceinline__ void fast_shift_strided_body(co
             sum[j] = sqr_add_ru<U>(ai, sum[j]);
         }
     };
-    if (row0 < rows) {
-        const T* x = X + row0;
-        const bool vec = row0 + RPL <= rows && ((reinterpret_cast<uintptr_t>(x) | (ld * sizeof(T))) & 15u) == 0;
-        size_t col = ty;
-        if (vec) {
-            typedef unsigned V4 __attribute__((ext_vector_type(4)));
-            // loads in flight per thread: 8 x 16 bytes; 4-byte elements have half as many workgroups (8 x 4 rows each: 256 at 8192 rows,
-            // one per CU), so they keep 16 in flight (8192^2 float: 88 us = 3.0 TB/s with 8).  The order of the accumulation -- columns
-            // ascending per thread -- does not depend on the depth.
-            constexpr int UNR = sizeof(T) == 4 ? 16 : 8;
-            if constexpr (UNR > 8) {
-                for (; col + (UNR - 1) * 32 < k; col += UNR * 32) {
-                    V4 raw[UNR];
+    auto segment = [&](const T* Xs, const size_t lds) {
+        if (row0 < rows) {
+            const T* x = Xs + row0;
+            const bool vec = row0 + RPL <= rows && ((reinterpret_cast<uintptr_t>(x) | (lds * sizeof(T))) & 15u) == 0;
+            size_t col = ty;
+            if (vec) {
+                typedef unsigned V4 __attribute__((ext_vector_type(4)));
+                // loads in flight per thread: 8 x 16 bytes; 4-byte elements have half as many workgroups (8 x 4 rows each: 256 at 8192 rows,
+                // one per CU), so they keep 16 in flight (8192^2 float: 88 us = 3.0 TB/s with 8).  The order of the accumulation -- columns
+                // ascending per thread -- does not depend on the depth.
+                constexpr int UNR = sizeof(T) == 4 ? 16 : 8;
+                if constexpr (UNR > 8) {
+                    for (; col + (UNR - 1) * 32 < k; col += UNR * 32) {
+                        V4 raw[UNR];
 #pragma unroll
-                    for (int u = 0; u < UNR; ++u) raw[u] = *(const V4*)(x + (col + 32 * u) * ld);
+                        for (int u = 0; u < UNR; ++u) raw[u] = *(const V4*)(x + (col + 32 * u) * lds);
 #pragma unroll
-                    for (int u = 0; u < UNR; ++u) {
+                        for (int u = 0; u < UNR; ++u) {
+                            T v[RPL];
+                            __builtin_memcpy(v, &raw[u], 16);
+#pragma unroll
+                            for (int j = 0; j < RPL; ++j) take(v[j], j);
+                        }
+                    }
+                }
+                for (; col + 7 * 32 < k; col += 8 * 32) {
+                    V4 raw[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) raw[u] = *(const V4*)(x + (col + 32 * u) * lds);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
                         T v[RPL];
                         __builtin_memcpy(v, &raw[u], 16);
 #pragma unroll
                         for (int j = 0; j < RPL; ++j) take(v[j], j);
                     }
                 }
-            }
-            for (; col + 7 * 32 < k; col += 8 * 32) {
-                V4 raw[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) raw[u] = *(const V4*)(x + (col + 32 * u) * ld);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
+                for (; col < k; col += 32) {
                     T v[RPL];
-                    __builtin_memcpy(v, &raw[u], 16);
+                    const V4 raw = *(const V4*)(x + col * lds);
+                    __builtin_memcpy(v, &raw, 16);
 #pragma unroll
                     for (int j = 0; j < RPL; ++j) take(v[j], j);
                 }
-            }
-            for (; col < k; col += 32) {
-                T v[RPL];
-                const V4 raw = *(const V4*)(x + col * ld);
-                __builtin_memcpy(v, &raw, 16);
+            } else {
+                for (; col < k; col += 32) {
 #pragma unroll
-                for (int j = 0; j < RPL; ++j) take(v[j], j);
-            }
-        } else {
-            for (; col < k; col += 32) {
-#pragma unroll
-                for (int j = 0; j < RPL; ++j)
-                    if (row0 + j < rows) take(x[col * ld + j], j);
+                    for (int j = 0; j < RPL; ++j)
+                        if (row0 + j < rows) take(x[col * lds + j], j);
+                }
             }
         }
-    }
+    };
+    segment(X, ld);
+    if constexpr (SEG2) segment(X2, ld2);
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
         samax[ty][tx * RPL + j] = amax[j];
@@ -1683,6 +1869,12 @@ template <typename T> __global__ void __launch_bounds__(256) fast_shift_pair_ker
     else fast_shift_strided_body<T>(X, o.ld, o.rows, k, sft, log2P, bid);
 }
 
+// gemmul8_syr2k: one shift per row of [X | Z | X2] (a.X, b.X: the same form, the same rows), written to a.sft
+template <typename T> __global__ void __launch_bounds__(256) fast_shift_seg2_kernel(const ShiftOperand a, const ShiftOperand b, size_t k, float log2P) {
+    if (a.kmajor) fast_shift_kmajor_body<T, true>((const T*)a.X, a.ld, k, a.sft, log2P, blockIdx.x, (const T*)b.X, b.ld);
+    else fast_shift_strided_body<T, true>((const T*)a.X, a.ld, a.rows, k, a.sft, log2P, blockIdx.x, (const T*)b.X, b.ld);
+}
+
 hipError_t launch_fast_shift_pair(hipStream_t stream, int dtype, int backend, unsigned N, size_t k, const QuantOperand& A, const QuantOperand& B) {
     if (A.rows == 0 && B.rows == 0) return hipSuccess;
     const float log2P = backend == kINT8 ? GEMMUL8_LOG2P_INT8[N - 2] : GEMMUL8_LOG2P_FP8[N - 2];
@@ -1699,6 +1891,24 @@ hipError_t launch_fast_shift_pair(hipStream_t stream, int dtype, int backend, un
     case kF64: hipLaunchKernelGGL(fast_shift_pair_kernel<double>, grid, dim3(256), 0, stream, a, b, k, log2P, g_batch.ws); break;
     case kC32: hipLaunchKernelGGL(fast_shift_pair_kernel<float2>, grid, dim3(256), 0, stream, a, b, k, log2P, g_batch.ws); break;
     case kC64: hipLaunchKernelGGL(fast_shift_pair_kernel<double2>, grid, dim3(256), 0, stream, a, b, k, log2P, g_batch.ws); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_fast_shift_seg2(hipStream_t stream, int dtype, unsigned N, size_t k, const QuantOperand& A, const Seg2Planes& S) {
+    if (g_batch.batch != 1 || A.rows == 0 || !S.X2) return hipErrorInvalidValue;
+    const float log2P = GEMMUL8_LOG2P_INT8[N - 2];
+    const size_t rpb = 8 * (16 / (is_f32(dtype) ? 4 : 8) / (is_complex(dtype) ? 2 : 1));  // rows per workgroup of the row-strided form
+    const size_t blocks = A.kmajor ? A.rows : (A.rows + rpb - 1) / rpb;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    const ShiftOperand a{A.X, A.ld, A.rows, 0, A.sft, (unsigned)blocks, A.kmajor ? 1 : 0}, b{S.X2, S.ld2, A.rows, 0, nullptr, 0, a.kmajor};
+    const dim3 grid((unsigned)blocks);
+    switch (dtype) {
+    case kF32: hipLaunchKernelGGL(fast_shift_seg2_kernel<float>, grid, dim3(256), 0, stream, a, b, k, log2P); break;
+    case kF64: hipLaunchKernelGGL(fast_shift_seg2_kernel<double>, grid, dim3(256), 0, stream, a, b, k, log2P); break;
+    case kC32: hipLaunchKernelGGL(fast_shift_seg2_kernel<float2>, grid, dim3(256), 0, stream, a, b, k, log2P); break;
+    case kC64: hipLaunchKernelGGL(fast_shift_seg2_kernel<double2>, grid, dim3(256), 0, stream, a, b, k, log2P); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

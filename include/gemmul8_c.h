@@ -185,6 +185,31 @@ GEMMUL8_API int gemmul8_herk(void *stream, int dtype, int backend, int uplo, int
                              size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode, void *work,
                              double *timers_ns);
 
+/* Symmetric rank-2k update of one triangle: C = alpha*(A*B^T + B*A^T) + beta*C (trans = N, A and B are n x k) or
+ * C = alpha*(A^T*B + B^T*A) + beta*C (trans = T, A and B are k x n); the plain transpose for the complex types too (HER2K, which applies alpha to one term
+ * and conj(alpha) to the other, is not one GEMM with one scalar and is not provided).  All four types; uplo and trans as in gemmul8_syrk (N / T only,
+ * the 0 / 1 and the hipBLAS values).  INT8 backend only (GEMMUL8_FP8: GEMMUL8_E_UNSUPPORTED, for gemmul8_syrk's reason).
+ *   - The identity: A B^T + B A^T = P Q^T with P = [A, Z, B, Z] and Q = [B, Z, A, Z], Z = the n x (kh - k) zero block, kh = k rounded up to a multiple
+ *     of 256 -- P and Q are n x 2 kh, and the second half of each starts on a 256 boundary (trans = T: everything transposed, P^T Q).
+ *   - The triangle named by uplo, diagonal included, holds bit for bit what
+ *     gemmul8_gemm(dtype, GEMMUL8_INT8, trans, trans == N ? T : N, n, n, 2 kh, alpha, P, ldP, Q, ldQ, beta, C, ldc, ...) in non-finite mode 0 puts
+ *     there with P and Q materialised.  No byte of the other strict triangle of C or of the ldc padding is read or written; beta == 0 never reads C.
+ *   - P and Q are never materialised: A and B are read where they lie, once per phase each, and every element leaves to the planes of both sides (Q's planes
+ *     are P's with the two K halves swapped).  The residue GEMMs run over the 256 x 256 tiles that touch the triangle only; the accurate mode's bound
+ *     GEMM stays the full square.
+ *   - Row i of A and row i of B (trans = T: the columns) share ONE shift, as the rows of P do: a row of A far smaller than the same row of B loses bits
+ *     that it would keep in a GEMM of its own.  The error is bounded against |P| |Q|^T = |A| |B|^T + |B| |A|^T, as for any GEMM of this library.
+ *   - A == B (the same pointer) is allowed.
+ *   - `work` holds gemmul8_work_size(is_complex, GEMMUL8_INT8, n, n, 2 kh, num_moduli, 0, 0, NULL, NULL) bytes: the equivalent GEMM's workspace.
+ *   - alpha / beta host or device pointers, timers_ns, stream order and capture safety (timers_ns == NULL) as in gemmul8_syrk.
+ *   - n == 0 or k == 0: GEMMUL8_OK, C untouched.  Bad uplo / trans, a null pointer, k > 2^16 (the equivalent GEMM's inner dimension 2 kh must stay
+ *     <= 2^17): GEMMUL8_E_ARG, answered before any HIP call.
+ *   - gemmul8_set_nonfinite_mode is ignored: the call behaves as mode 0.
+ * No counterpart in the reference (it emulates GEMM only). */
+GEMMUL8_API int gemmul8_syr2k(void *stream, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void *alpha, const void *A,
+                              size_t lda, const void *B, size_t ldb, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
+                              void *work, double *timers_ns);
+
 /* D(i, j) += bias[i] for a column-major m x n real matrix: the broadcast bias of a hipblasLtMatmul BIAS epilogue, applied by the hook after
  * the emulated GEMM (one more rounding than the vendor's fused form).  S / D only.  No counterpart in the reference. */
 GEMMUL8_API int gemmul8_add_row_bias(void *stream, int dtype, size_t m, size_t n, void *D, size_t ldd, const void *bias);

@@ -1,0 +1,60 @@
+"""-m gpu: hipblas{S,D}syr2k under LD_PRELOAD (tests/cpp/test_hook_syr2k.cpp, compiled here): emulated calls equal the direct gemmul8_syr2k bit for
+bit and leave the other triangle alone; the FP8 backend and k > 2^16 reach the native routine (exact small-integer answer); a numeric
+GEMMUL8_MIN_FLOPS is a floor on 2 n (n + 1) k; GEMMUL8_HOOK_STATS counts the SYR2K calls on a line of its own."""
+import os
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "test_hook_syr2k.cpp")
+LIB = os.path.join(ROOT, "gemmul8_amd", "lib", "libgemmul8.so")
+HIPCC = "/opt/rocm/bin/hipcc"
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("hook_syr2k") / "test_hook_syr2k")
+    subprocess.run([HIPCC, "-std=c++20", "-O2", "-Wno-unused-value", "-x", "hip", "--offload-arch=gfx950", SRC, "-o", out, "-lhipblas", "-ldl"], check=True)
+    return out
+
+
+def run(cmd, env_extra):
+    env = dict(os.environ)
+    env.pop("GEMMUL8_MIN_FLOPS", None)
+    env.update({"LD_PRELOAD": LIB, "GEMMUL8_NUM_MOD_D": "15", "GEMMUL8_NUM_MOD_S": "8", "GEMMUL8_HOOK_STATS": "1"})
+    env.update(env_extra)
+    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
+    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    print(p.stdout)
+    assert p.returncode == 0 and "ALL OK" in p.stdout, p.stdout[-2000:]
+    return p.stdout
+
+
+def test_hooked_syr2k_equals_the_direct_call(exe):
+    out = run([exe, "emu"], {})
+    assert "bitwise" in out
+    assert "stats: emulated 4 SYR2K calls" in out and "native 0 SYR2K calls" in out, out[-2000:]
+    assert "SYRK calls" not in out and "HERK calls" not in out   # a routine that was not seen has no line
+
+
+def test_fp8_backend_reaches_the_native_routine(exe):
+    out = run([exe, "native", "64"], {"GEMMUL8_BACKEND": "1"})
+    assert "passed to the native routine" in out and "SYR2K is emulated on the INT8 backend" in out
+    assert "stats: emulated 0 SYR2K calls" in out and "native 2 SYR2K calls" in out, out[-2000:]
+
+
+def test_k_beyond_the_range_reaches_the_native_routine(exe):
+    out = run([exe, "native", str((1 << 16) + 8)], {})
+    assert "passed to the native routine" in out and "SYR2K is emulated on the INT8 backend for k <= 65536 only" in out
+    assert "stats: emulated 0 SYR2K calls" in out and "native 2 SYR2K calls" in out, out[-2000:]
+
+
+def test_floor_on_2_n_n1_k(exe):
+    """GEMMUL8_MIN_FLOPS as a number is a floor on 2 n (n + 1) k: 2 * 8 * 9 * 64 = 9216 is below 9300 -> native, exact, and said once; the emulated
+    program's 2 * 300 * 301 * 200 = 36120000 meets a floor of exactly that (twice what a floor on n (n + 1) k would see) -> all four calls emulated"""
+    out = run([exe, "native", "64"], {"GEMMUL8_MIN_FLOPS": "9300"})
+    assert "native 2 SYR2K calls" in out and out.count("SYR2K n = 8, k = 64") == 1 and "stays on the native routine" in out, out[-2000:]
+    out = run([exe, "emu"], {"GEMMUL8_MIN_FLOPS": "36120000"})
+    assert "emulated 4 SYR2K calls" in out and "stays on the native routine" not in out, out[-2000:]

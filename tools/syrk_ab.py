@@ -4,7 +4,9 @@ n = 16384 k = 512, 14 moduli, accurate and fast mode.  The GEMM side may come fr
 commit's), loaded in the same process; a second GEMM column of this build shows that the GEMM itself did not move.  Per-phase timers
 (timers_ns: scaling, low-precision GEMMs, CRT) of one extra call each are printed beside the medians.
 --herk: gemmul8_herk against gemmul8_gemm(A, A^H) instead -- ZHERK n = k = 8192 at 20 moduli and CHERK at 13 (--shapes / --moduli / --types override).
-usage: python tools/syrk_ab.py [--herk] [--gemm-lib parent/libgemmul8.so] [--rounds 9] [--shapes 8192x8192,8192x1024,16384x512] [--moduli 14] [--out FILE]"""
+--syr2k: gemmul8_syr2k against what replaced it before the routine existed -- gemmul8_gemm on the materialised P = [A, Z, B, Z] and Q = [B, Z, A, Z]
+(the GEMM alone, and with the two packing copies in front of it) -- and against the native hipblas?syr2k: D, 14 moduli, n = 8192 with k = 4096 and k = 512.
+usage: python tools/syrk_ab.py [--herk | --syr2k] [--gemm-lib parent/libgemmul8.so] [--rounds 9] [--shapes 8192x8192,8192x1024,16384x512] [--moduli 14] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -23,6 +25,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--gemm-lib", default=None)
 ap.add_argument("--rounds", type=int, default=9)
 ap.add_argument("--herk", action="store_true")
+ap.add_argument("--syr2k", action="store_true")
 ap.add_argument("--shapes", default=None)
 ap.add_argument("--moduli", type=int, default=None, help="default: 14 (SYRK); --herk: 20 for Z, 13 for C")
 ap.add_argument("--types", default=None, help="SYRK: D; --herk: Z,C")
@@ -37,11 +40,91 @@ if a.gemm_lib:
     other.gemmul8_gemm.restype = C.c_int
     other.gemmul8_gemm.argtypes = this.gemmul8_gemm.argtypes
 st = torch.cuda.current_stream().cuda_stream
-TYPES = {"D": (g.D, torch.float64, np.float64, np.float64), "Z": (g.Z, torch.complex128, np.complex128, np.float64),
+TYPES = {"S": (g.S, torch.float32, np.float32, np.float32), "D": (g.D, torch.float64, np.float64, np.float64), "Z": (g.Z, torch.complex128, np.complex128, np.float64),
          "C": (g.Cx, torch.complex64, np.complex64, np.float32)}   # code, tensor type, GEMM scalar type, rank-k scalar type
+
+
+def native_syr2k(ty):
+    """hipblas{S,D}syr2k on the current stream through the hipBLAS this process has mapped (PyTorch's copy), else the system's"""
+    path = "libhipblas.so"
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libhipblas.so" in line:
+                path = line.split()[-1]
+                break
+    hb = C.CDLL(path)
+    handle = C.c_void_p()
+    assert hb.hipblasCreate(C.byref(handle)) == 0 and hb.hipblasSetStream(handle, C.c_void_p(st)) == 0
+    fn = getattr(hb, f"hipblas{ty}syr2k")
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    return lambda n, k, al, A, B, be, Cm: fn(handle, 122, 111, n, k, al.ctypes.data, A.data_ptr(), n, B.data_ptr(), n, be.ctypes.data, Cm.data_ptr(), n)
+
+
+def syr2k_ab():
+    rows = []
+    for ty, shape in ((t, s) for t in (a.types or "D").split(",") for s in (a.shapes or "8192x4096,8192x512").split(",")):
+        code, tdt, gdt, _ = TYPES[ty]
+        N = a.moduli or 14
+        al, be = np.array([1.0], dtype=gdt), np.array([0.0], dtype=gdt)
+        n, k = (int(x) for x in shape.split("x"))
+        kh = (k + 255) // 256 * 256
+        A, B = (torch.randn((k, n), dtype=tdt, device="cuda") for _ in range(2))   # column-major n x k
+        P, Q = (torch.zeros((2 * kh, n), dtype=tdt, device="cuda") for _ in range(2))
+
+        def pack():
+            P[:k], P[kh:kh + k], Q[:k], Q[kh:kh + k] = A, B, B, A
+        pack()
+        Cout = torch.zeros((n, n), dtype=tdt, device="cuda")
+        work = torch.empty(g.syr2k_work_size(tdt.is_complex, n, k, N), dtype=torch.uint8, device="cuda")
+        native = native_syr2k(ty) if ty in "SD" else None
+        for fast in (0, 1):
+            def gemm(tm=None):
+                return this.gemmul8_gemm(st, code, g.INT8, 0, 1, n, n, 2 * kh, al.ctypes.data, P.data_ptr(), n, Q.data_ptr(), n, be.ctypes.data, Cout.data_ptr(), n, N,
+                                         fast, work.data_ptr(), None, None, 0, 0, 0, 0, tm)
+
+            def pack_gemm(tm=None):
+                pack()
+                return gemm(tm)
+
+            def syr2k(tm=None):
+                return this.gemmul8_syr2k(st, code, g.INT8, 0, 0, n, k, al.ctypes.data, A.data_ptr(), n, B.data_ptr(), n, be.ctypes.data, Cout.data_ptr(), n, N, fast,
+                                          work.data_ptr(), tm)
+            legs = [("syr2k", syr2k), ("gemm_pq", gemm), ("pack_gemm_pq", pack_gemm)]
+            if native and not fast:
+                legs.append(("native", lambda tm=None: native(n, k, al, A, B, be, Cout)))
+            ts = {name: [] for name, _ in legs}
+            for r in range(a.rounds + 2):
+                for name, fn in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    rc = fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    assert rc == 0, (name, rc)
+                    if r >= 2:
+                        ts[name].append(e0.elapsed_time(e1))
+            rec = {"type": ty, "n": n, "k": k, "moduli": N, "mode": "fast" if fast else "accurate", "rounds": a.rounds}
+            for name, fn in legs:
+                t = sorted(ts[name])
+                rec[name + "_ms"] = round(t[len(t) // 2], 4)
+                rec[name + "_min_ms"] = round(t[0], 4)
+                if name in ("syr2k", "gemm_pq"):
+                    tm = (C.c_double * 4)()
+                    assert fn(tm) == 0
+                    rec[name + "_phases_ms"] = {"scale": round(tm[0] * 1e-6, 4), "lowprec_gemm": round(tm[1] * 1e-6, 4), "crt": round(tm[3] * 1e-6, 4)}
+            rec["syr2k_over_gemm_pq"] = round(rec["syr2k_ms"] / rec["gemm_pq_ms"], 4)
+            rec["syr2k_over_pack_gemm_pq"] = round(rec["syr2k_ms"] / rec["pack_gemm_pq_ms"], 4)
+            if "native_ms" in rec:
+                rec["syr2k_over_native"] = round(rec["syr2k_ms"] / rec["native_ms"], 4)
+            rows.append(rec)
+            print(json.dumps(rec), flush=True)
+    return rows
+
+
 shapes = a.shapes or ("8192x8192" if a.herk else "8192x8192,8192x1024,16384x512")
-rows = []
-for ty, shape in ((t, s) for t in (a.types or ("Z,C" if a.herk else "D")).split(",") for s in shapes.split(",")):
+rows = syr2k_ab() if a.syr2k else []
+for ty, shape in ((t, s) for t in (() if a.syr2k else (a.types or ("Z,C" if a.herk else "D")).split(",")) for s in shapes.split(",")):
     code, tdt, gdt, rdt = TYPES[ty]
     N = a.moduli or ((20 if ty == "Z" else 13) if a.herk else 14)
     al, be = np.array([1.0], dtype=gdt), np.array([0.0], dtype=gdt)      # the GEMM's scalars (complex for Z / C)
