@@ -29,7 +29,8 @@
 //                                  once        workspace pre-sizing, applied when a SKIP_SCALE switch is on (hook.cu:232-281,656-662)
 //  the rest is this build's only:
 //   GEMMUL8_FP8_BOUND, GEMMUL8_NONFINITE
-//                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace)
+//                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace); under `ieee` SYRK / HERK / SYR2K
+//                                              calls are not emulated (try_syrk_impl)
 //   GEMMUL8_MIN_FLOPS              per call    unset or 0 = emulate every selected call (the reference's behaviour); `auto` = a fitted cost model decides
 //                                              per call (below_floor); a number = floor on 2*m*n*k.  The first call a floor declines is logged once.
 //   GEMMUL8_DIST                   per call    blocks | moduli | fp64sum: shard every emulated GEMM over the ranks of an SPMD job (try_dist)
@@ -323,6 +324,15 @@ bool selection_from_env(int dtype, Selection* s) {
 constexpr int kMaxK = 1 << 17, kMaxKFp8 = 65536;
 bool k_in_range(const GemmCall& c, const Selection& s) { return c.k <= (s.backend == GEMMUL8_FP8 ? kMaxKFp8 : kMaxK); }
 
+// GEMMUL8_NONFINITE=ieee, read once.  Kept here and not asked of the library: one linked with this file may lack gemmul8_set_nonfinite_mode.
+bool nonfinite_ieee() {
+    static const bool on = [] {
+        const char* nf = std::getenv("GEMMUL8_NONFINITE");
+        return nf && !std::strcmp(nf, "ieee");
+    }();
+    return on;
+}
+
 // process-wide workspace floor, computed once (hook.cu:232-281)
 size_t g_maxA = 0, g_maxB = 0, g_maxC = 0;
 std::once_flag g_max_once;
@@ -334,8 +344,9 @@ void init_max_workspace() {
             if (!std::strcmp(fb, "reference")) (void)abi().set_fp8_bound_mode(1);
         // GEMMUL8_NONFINITE=ieee: BLAS-like NaN / Inf propagation (include/gemmul8_c.h, gemmul8_set_nonfinite_mode); unset or `reference`: mode 0.
         // Not applied to the calls the multi-GPU plans take (GEMMUL8_DIST).
+        // The rank-k entry points have no mode 1: their calls stay on the native routine under `ieee` (try_syrk_impl).
         if (const char* nf = std::getenv("GEMMUL8_NONFINITE"); nf && *nf) {
-            if (!std::strcmp(nf, "ieee")) {
+            if (nonfinite_ieee()) {
                 if (auto set = abi().set_nonfinite_mode) (void)set(1);
             } else if (std::strcmp(nf, "reference")) {
                 std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=%s not understood (ieee | reference): non-finite mode 0\n", nf);
@@ -722,7 +733,7 @@ bool try_emulate(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* sta
 // (real alpha, beta) through gemmul8_herk (no counterpart in the reference).  One body; herm selects the entry point, the operations that are taken
 // (N / T, N / C) and the name in the log lines.
 // Selection: the type's GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, k > 2^17, a moduli count outside
-// the type's range (each said once per routine), a fill mode or operation other than upper / lower and N / T (HERK: N / C), a dimension an int cannot
+// the type's range, GEMMUL8_NONFINITE=ieee (each said once per routine), a fill mode or operation other than upper / lower and N / T (HERK: N / C), a dimension an int cannot
 // hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: below_floor's SYRK / HERK form.  GEMMUL8_DIST and the skip-scaling switches do not apply.
 // hipblas{S,D,C,Z}syr2k (kind = kSYR2K; B != nullptr): one triangle of alpha (A B^T + B A^T) + beta C through gemmul8_syr2k -- the same selection, with
 // k <= 2^16 (the equivalent GEMM's inner dimension is 2 pad256(k)), that GEMM's workspace, and below_floor's SYR2K form.
@@ -750,6 +761,14 @@ bool try_syrk_impl(int kind, hipblasHandle_t handle, int dtype, int uplo, int tr
         std::call_once(told[kind][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
             std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for k <= %d only (GEMMUL8_BACKEND=%d, k=%d): using the native routine "
                                  "for such calls\n", name, max_k, s.backend, k);
+        });
+        return false;
+    }
+    if (nonfinite_ieee()) {  // gemmul8_syrk / herk / syr2k ignore the non-finite mode: a NaN or Inf operand would come back as finite numbers
+        static std::once_flag told[3];
+        std::call_once(told[kind], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: %s has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
+                                 "for such calls\n", name);
         });
         return false;
     }

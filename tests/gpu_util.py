@@ -381,3 +381,181 @@ def parity_case_embedded(A, B, C0, N, fastmode, opA, opB, alpha, beta, backend, 
     assert bits_equal(oC[~mk], bufC[~mk])
     assert bits_equal(Cdev[mk], oC[mk]), f"final C differs in {np.sum(Cdev[mk] != oC[mk])} elements"
     return nd, it["lo_format"]
+
+
+# ---- the rank-k entry points (gemmul8_syrk / gemmul8_herk / gemmul8_syr2k): one driver, and the three checks of their suites
+RANK_K = ("syrk", "herk", "syr2k")
+SENTINEL = 0xA5
+LDC_EXTRA = (1, 7, 64)
+
+
+def pad256(k):
+    return (k + 255) // 256 * 256
+
+
+def rank_k_inner(routine, k):
+    """inner dimension of the GEMM whose workspace layout (and oracle cost) a rank-k call has"""
+    return 2 * pad256(k) if routine == "syr2k" else k
+
+
+def rank_k_work_size(routine, cplx, n, k, N):
+    return g.work_size(cplx, g.INT8, n, n, rank_k_inner(routine, k), N)[0]
+
+
+def tri_mask(n, uplo):
+    """[row][col]: True inside the stored triangle, diagonal included"""
+    i, j = np.indices((n, n))
+    return i >= j if uplo == "L" else i <= j
+
+
+def rank_k_call(routine, dt, n, k, uplo, trans, N, fast, alpha, beta, dA, lda, dC, ldc, dB=None, ldb=0, offA=0, offB=0, offC=0, scalars_dev=False, work=None):
+    """One call of a rank-k C entry point.  dA, dB, dC: device tensors that hold the buffers the operands live in (any shape and element type; `dC` comes in
+    sentinel-filled, see sentinel_c, and is updated in place); lda / ldb / ldc and the base offsets off* are in ELEMENTS of `dt`.  alpha, beta: python
+    scalars, passed as host or device pointers of the routine's scalar type (HERK: the real type of `dt`'s width).  Returns the workspace (a fresh one,
+    filled with 0x3C, unless given); the caller synchronises."""
+    dt = np.dtype(dt)
+    esz = dt.itemsize
+    sdt = np.dtype(np.float32 if esz == 8 else np.float64) if routine == "herk" else dt
+    al, be = np.array([alpha], dtype=sdt), np.array([beta], dtype=sdt)
+    keep = (al, be)
+    if scalars_dev:
+        keep = (torch.from_numpy(al).cuda(), torch.from_numpy(be).cuda())
+        pa, pb = keep[0].data_ptr(), keep[1].data_ptr()
+    else:
+        pa, pb = al.ctypes.data, be.ctypes.data
+    if work is None:
+        work = torch.full((rank_k_work_size(routine, dt.kind == "c", n, k, N),), 0x3C, dtype=torch.uint8, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    head = (st, ol.DT[dt], g.INT8, g.UPLO[uplo], g.OPS[trans], n, k, pa, dA.data_ptr() + offA * esz, lda)
+    tail = (pb, dC.data_ptr() + offC * esz, ldc, N, int(fast), work.data_ptr(), None)
+    if routine == "syr2k":
+        rc = g.lib().gemmul8_syr2k(*head, dB.data_ptr() + offB * esz, ldb, *tail)
+    else:
+        rc = getattr(g.lib(), "gemmul8_" + routine)(*head, *tail)
+    g.check(rc, "gemmul8_" + routine)
+    if scalars_dev:
+        torch.cuda.synchronize()   # the device scalars stay alive until the call has read them
+    return work
+
+
+def sentinel_c(C0, uplo, ld_extra, off=0, tail=3):
+    """The C buffer of a rank-k call: off + (n + ld_extra) * n + tail elements, every byte SENTINEL except the triangle `uplo` of the n x n window at element
+    `off`, which holds C0's.  Returns (bytes uint8 [elements][esz], ldc, inside) with inside[element] True on the triangle's elements."""
+    n = C0.shape[0]
+    esz = C0.dtype.itemsize
+    ldc = n + ld_extra
+    buf = np.full((off + ldc * n + tail, esz), SENTINEL, np.uint8)
+    inside = np.zeros(buf.shape[0], bool)
+    mk = tri_mask(n, uplo)
+    inside[off:off + ldc * n].reshape(n, ldc)[:, :n] = mk.T
+    buf[off:off + ldc * n].reshape(n, ldc, esz)[:, :n][mk.T] = np.ascontiguousarray(C0.T).view(np.uint8).reshape(n, n, esz)[mk.T]
+    return buf, ldc, inside
+
+
+def rank_k_equivalent(routine, A, B, trans):
+    """(P, Q, opP, opQ): the GEMM a rank-k call is defined by -- SYRK A A^T, HERK A A^H, SYR2K the K-concatenated P Q^T of tests/test_syr2k_premise.py"""
+    if routine == "syr2k":
+        from test_syr2k_premise import concat
+        P, Q, _ = concat(A, B, trans)
+        return P, Q, trans, "T" if trans == "N" else "N"
+    return A, A, trans, ("C" if routine == "herk" else "T") if trans == "N" else "N"
+
+
+def window_bytes(out, n, ldc, off):
+    """the n x n window of a C buffer's bytes as [col][row][esz]"""
+    return out[off:off + ldc * n].reshape(n, ldc, -1)[:, :n]
+
+
+def triangle_differs(routine, got, ref, uplo):
+    """(a) / (b): [col][row] mask of the stored triangle's entries whose bytes differ from the GEMM's `ref` (numpy n x n).  HERK: the diagonal is compared
+    in its real part only, and its imaginary part must be all-zero bits (+0.0)."""
+    n = ref.shape[0]
+    esz = ref.dtype.itemsize
+    refb = np.ascontiguousarray(ref.T).view(np.uint8).reshape(n, n, esz)
+    ne = got != refb
+    if routine == "herk":
+        d = np.arange(n)
+        assert not got[d, d, esz // 2:].any(), "a diagonal imaginary part is not +0.0"
+        ne[d, d, esz // 2:] = False
+    return ne.any(axis=2) & tri_mask(n, uplo).T
+
+
+def _rank_k_marked_work(routine, code, n, k, N):
+    """A workspace whose every byte is 0x3C -- so that zero padding and SYR2K's zero block read as zero only if the call wrote them -- but for the plane sets
+    of the equivalent GEMM's B_lo that the routine never writes (SYRK: all, HERK: part 0), which read_intermediates expects zero"""
+    cplx = code >= 2
+    kk = rank_k_inner(routine, k)
+    work = torch.full((g.work_size(cplx, g.INT8, n, n, kk, N)[0],), 0x3C, dtype=torch.uint8, device="cuda")
+    L = g.Layout()
+    g.check(g.lib().gemmul8_get_layout(code, g.INT8, n, n, kk, N, work.data_ptr(), None, None, 0, 0, C.byref(L)))
+    for p in range({"syrk": L.parts, "herk": 1, "syr2k": 0}[routine]):
+        off = L.B_lo + p * L.part_strideB - work.data_ptr()
+        work[off:off + L.num_mat * L.sizeB] = 0
+    return work
+
+
+def rank_k_case(routine, A, B, C0, uplos, trans, N, fast, alpha, beta, ld_extra=(0, 0, 1), base_off=(0, 0, 0), scalars_dev=False, oracle=True, rng=None,
+                nan_diag=True, intermediates=False, gemm=True):
+    """The three checks of the rank-k suites on one case, every `uplo` of `uplos` against ONE equivalent GEMM: (a) the stored triangle equals gemmul8_gemm
+    run in the same process, (b) (oracle=True) it equals the CPU oracle's GEMM fed with the device GEMM's shifts, and that GEMM's C is finite, (c) every
+    byte of the sentinel-filled C buffer outside the triangle is unchanged; and the buffers A and B are embedded in (ld = rows + ld_extra, base offset in
+    elements, random finite data around them) are byte-identical after the call.  A, B (None but for SYR2K; `B is A` passes the same pointer), C0: numpy,
+    as stored.  HERK: C0's diagonal is real and, with nan_diag, the call sees NaN in the diagonal's imaginary parts.  gemm=False: no GEMM, (c) and the
+    operand buffers only (a caller that compares two runs of the same call).  Returns {"out": {uplo: bytes of the C buffer after the call}, "tri": {uplo:
+    [col][row] mask}, "it": {uplo: the call's intermediates in its own layout, with intermediates=True -- which also
+    holds its shifts and planes against the equivalent GEMM's}, "gemm": the device GEMM's C}."""
+    rng = rng or np.random.default_rng(1)
+    dt = A.dtype
+    n, k = A.shape if trans == "N" else A.shape[::-1]
+    exa, exb, exc = ld_extra
+    offa, offb, offc = base_off
+    bufA, lda = embed(A, exa, offa, rng)
+    dA = torch.from_numpy(bufA.copy()).cuda()
+    if routine == "syr2k" and B is not A:
+        bufB, ldb = embed(B, exb, offb, rng)
+        dB = torch.from_numpy(bufB.copy()).cuda()
+    else:
+        bufB, ldb, dB, offb = bufA, lda, dA, offa
+    assert not oracle or gemm
+    Cg = Co = None
+    if gemm:
+        P, Q, opP, opQ = rank_k_equivalent(routine, A, B, trans)
+        Cg = hip_gemm(P, Q, N, fastmode=fast, opA=opP, opB=opQ, alpha=alpha, beta=beta, C0=C0, want_intermediates=oracle or intermediates)
+        if oracle or intermediates:
+            Cg, itg = Cg
+    if oracle:
+        Co = np.asarray(ol.gemm(P, Q, N, fastmode=fast, opA=opP, opB=opQ, alpha=alpha, beta=beta, C0=C0, sftA_in=itg["sftA"], sftB_in=itg["sftB"]))
+        assert np.isfinite(Co).all(), "the oracle's C is not finite: the case's data leaves the type's range"
+    Cin = C0
+    if routine == "herk" and nan_diag:
+        Cin = C0.copy()
+        Cin.imag[np.arange(n), np.arange(n)] = np.nan
+    res = dict(out={}, tri={}, it={}, gemm=Cg)
+    code = ol.DT[dt]
+    for uplo in uplos:
+        before, ldc, inside = sentinel_c(Cin, uplo, exc, offc)
+        dC = torch.from_numpy(before.copy()).cuda()
+        work = _rank_k_marked_work(routine, code, n, k, N) if intermediates else None
+        work = rank_k_call(routine, dt, n, k, uplo, trans, N, fast, alpha, beta, dA, lda, dC, ldc, dB, ldb, offa, offb, offc, scalars_dev, work)
+        torch.cuda.synchronize()
+        out = dC.cpu().numpy()
+        what = f"{routine} {dt.name} n={n} k={k} uplo={uplo} trans={trans} N={N} fast={fast} scalars=({alpha}, {beta}) ld={ld_extra} off={base_off}"
+        assert bits_equal(dA.cpu().numpy(), bufA) and bits_equal(dB.cpu().numpy(), bufB), "an operand buffer was written: " + what
+        assert np.array_equal(out[~inside], before[~inside]), "bytes outside the stored triangle were written: " + what                          # (c)
+        got = window_bytes(out, n, ldc, offc)
+        for ref, name in ((Cg, "the equivalent gemmul8_gemm"), (Co, "the oracle's GEMM")):                                                       # (a), (b)
+            if ref is not None:
+                bad = triangle_differs(routine, got, ref, uplo)
+                assert not bad.any(), f"{bad.sum()} entries of the triangle differ from {name}, first at (col, row) {np.argwhere(bad)[:3].tolist()}: " + what
+        res["out"][uplo] = got.copy()
+        res["tri"][uplo] = tri_mask(n, uplo).T
+        if intermediates:
+            it = res["it"][uplo] = read_intermediates(work, code, g.INT8, n, n, rank_k_inner(routine, k), N)
+            if gemm:   # the one operand pass leaves the equivalent GEMM's shifts and planes: all of A_lo; of B_lo what the routine does not alias (SYRK: nothing, HERK: parts 1, 2)
+                assert np.array_equal(it["sftA"], itg["sftA"]) and np.array_equal(itg["sftB"], itg["sftA"]), "sftA differs from the equivalent GEMM's: " + what
+                assert np.array_equal(it["A_lo"], itg["A_lo"]), "A_lo differs from the equivalent GEMM's: " + what
+                first = {"syrk": 3, "herk": 1, "syr2k": 0}[routine]
+                assert np.array_equal(it["B_lo"][first:], itg["B_lo"][first:]), "the right-hand planes differ from the equivalent GEMM's B_lo: " + what
+                if routine == "herk":
+                    assert not it["B_lo"][0].any(), "part 0 of B_lo, which HERK aliases to A_lo's, was written: " + what
+    return res

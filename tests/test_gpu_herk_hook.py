@@ -51,3 +51,11 @@ def test_k_beyond_the_range_reaches_the_native_routine(exe):
     out = run([exe, "native", str((1 << 17) + 8)], {})
     assert "passed to the native routine" in out and "HERK is emulated on the INT8 backend" in out
     assert "stats: emulated 0 HERK calls" in out and "native 2 HERK calls" in out, out[-2000:]
+
+
+def test_ieee_nonfinite_mode_reaches_the_native_routine(exe):
+    """GEMMUL8_NONFINITE=ieee promises BLAS-like NaN / Inf propagation and gemmul8_herk has no such mode: the hook leaves HERK to the native routine (exact
+    small-integer answer), says so once and counts the calls as native"""
+    out = run([exe, "native", "64"], {"GEMMUL8_NONFINITE": "ieee"})
+    assert "passed to the native routine" in out and out.count("GEMMUL8_NONFINITE=ieee: HERK has no NaN / Inf propagation mode and is NOT emulated") == 1
+    assert "stats: emulated 0 HERK calls" in out and "native 2 HERK calls" in out, out[-2000:]

@@ -58,3 +58,11 @@ def test_floor_on_2_n_n1_k(exe):
     assert "native 2 SYR2K calls" in out and out.count("SYR2K n = 8, k = 64") == 1 and "stays on the native routine" in out, out[-2000:]
     out = run([exe, "emu"], {"GEMMUL8_MIN_FLOPS": "36120000"})
     assert "emulated 4 SYR2K calls" in out and "stays on the native routine" not in out, out[-2000:]
+
+
+def test_ieee_nonfinite_mode_reaches_the_native_routine(exe):
+    """GEMMUL8_NONFINITE=ieee promises BLAS-like NaN / Inf propagation and gemmul8_syr2k has no such mode: the hook leaves SYR2K to the native routine (exact
+    small-integer answer), says so once and counts the calls as native"""
+    out = run([exe, "native", "64"], {"GEMMUL8_NONFINITE": "ieee"})
+    assert "passed to the native routine" in out and out.count("GEMMUL8_NONFINITE=ieee: SYR2K has no NaN / Inf propagation mode and is NOT emulated") == 1
+    assert "stats: emulated 0 SYR2K calls" in out and "native 2 SYR2K calls" in out, out[-2000:]

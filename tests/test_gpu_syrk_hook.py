@@ -54,3 +54,11 @@ def test_floor_on_n_n1_k(exe):
     """GEMMUL8_MIN_FLOPS as a number is a floor on n (n + 1) k: 8 * 9 * 64 = 4608 is below 5000 -> native, exact"""
     out = run([exe, "native", "64"], {"GEMMUL8_MIN_FLOPS": "5000"})
     assert "native 2 SYRK calls" in out and "stays on the native routine" in out, out[-2000:]
+
+
+def test_ieee_nonfinite_mode_reaches_the_native_routine(exe):
+    """GEMMUL8_NONFINITE=ieee promises BLAS-like NaN / Inf propagation and gemmul8_syrk has no such mode: the hook leaves SYRK to the native routine (exact
+    small-integer answer), says so once and counts the calls as native"""
+    out = run([exe, "native", "64"], {"GEMMUL8_NONFINITE": "ieee"})
+    assert "passed to the native routine" in out and out.count("GEMMUL8_NONFINITE=ieee: SYRK has no NaN / Inf propagation mode and is NOT emulated") == 1
+    assert "stats: emulated 0 SYRK calls" in out and "native 2 SYRK calls" in out, out[-2000:]
