@@ -559,3 +559,183 @@ def rank_k_case(routine, A, B, C0, uplos, trans, N, fast, alpha, beta, ld_extra=
                 if routine == "herk":
                     assert not it["B_lo"][0].any(), "part 0 of B_lo, which HERK aliases to A_lo's, was written: " + what
     return res
+
+
+# ---- gemmul8_gemm_batched on views (tests/test_gpu_batched_paths.py): one driver and its three checks
+C_SENTINEL = {4: 0x7FC0BEEF, 8: 0x7FF8DEADBEEF0123}   # one fixed (quiet) NaN bit pattern per real component of the C buffer outside the windows
+ITEM_SCALE_STEP, ITEM_SCALE_MOD = 3, 11               # item b's operands are scaled by 2^(3 b mod 11): no two of eleven consecutive items share shifts
+
+
+def rand_spread(shape, dtype, rng):
+    """entries of mixed magnitude (a log-normal spread), both signs; complex types in both components"""
+    x = (rng.random(shape) - 0.5) * np.exp(rng.standard_normal(shape))
+    if np.dtype(dtype).kind == "c":
+        x = x + 1j * (rng.random(shape) - 0.5) * np.exp(rng.standard_normal(shape))
+    return x.astype(dtype)
+
+
+def stored_shape(op, rows, k):
+    """shape of the matrix as stored whose op() is rows x k (B: op(B)^T is n x k, so stored_shape of the opposite op)"""
+    return (rows, k) if op == "N" else (k, rows)
+
+
+def batched_data(dt, m, n, k, batch, opA="N", opB="N", shareA=False, shareB=False, rng=None, gen=rand_spread):
+    """Independent items as stored (numpy, before op): lists As, Bs (ONE entry for a shared operand, stride 0) and C0s.  Item b's own operands are scaled
+    by s = 2^(3 b mod 11), its C0 by s^2: the items' shifts differ, so that a mixed-up item offset cannot cancel."""
+    rng = rng or np.random.default_rng(0)
+    dt = np.dtype(dt)
+    sc = [2.0 ** (ITEM_SCALE_STEP * b % ITEM_SCALE_MOD) for b in range(batch)]
+    shA, shB = stored_shape(opA, m, k), stored_shape("T" if opB == "N" else "N", n, k)
+    As = [gen(shA, dt, rng)] if shareA else [(gen(shA, dt, rng) * s).astype(dt) for s in sc]
+    Bs = [gen(shB, dt, rng)] if shareB else [(gen(shB, dt, rng) * s).astype(dt) for s in sc]
+    C0s = [(gen((m, n), dt, rng) * s * s).astype(dt) for s in sc]
+    return As, Bs, C0s
+
+
+def _strided_buffer(items, count, pad, gap, head, fill, tail=4):
+    """`count` column-major windows in one 1-D buffer of the items' type: ld = rows + pad, item b at element head + b * stride, stride = ld * cols + gap
+    (0 when `items` holds the ONE matrix every item shares); every other element is `fill(size) -> array`.  Returns (buffer, ld, stride, inside mask)."""
+    rows, cols = items[0].shape
+    ld = rows + pad
+    shared = len(items) == 1 and count > 1
+    stride = 0 if shared else ld * cols + gap
+    size = head + (len(items) - 1) * stride + ld * cols + tail
+    buf = fill(size)
+    inside = np.zeros(size, bool)
+    for b, M in enumerate(items):
+        o = head + b * stride
+        buf[o:o + ld * cols].reshape(cols, ld)[:, :rows] = M.T
+        inside[o:o + ld * cols].reshape(cols, ld)[:, :rows] = True
+    return buf, ld, stride, inside
+
+
+def _fill_operand(dt, nan):
+    """what surrounds the windows of A and B: huge finite numbers of both signs, which would wreck the bounds and the residues if a kernel used one (non-finite
+    mode 1: NaN, which would flag a row or a column)"""
+    dt = np.dtype(dt)
+    big = np.nan if nan else (1e30 if dt.itemsize // (2 if dt.kind == "c" else 1) == 4 else 1e300)
+
+    def fill(size):
+        v = np.full(size, big, dt)
+        v[1::2] *= -1
+        if dt.kind == "c":
+            v = (v + 1j * v).astype(dt)
+        return v
+    return fill
+
+
+def _fill_c(dt):
+    dt = np.dtype(dt)
+    rsz = dt.itemsize // (2 if dt.kind == "c" else 1)
+
+    def fill(size):
+        v = np.empty(size, dt)
+        v.view(np.uint32 if rsz == 4 else np.uint64)[:] = C_SENTINEL[rsz]
+        return v
+    return fill
+
+
+def work_vectors(work, code, backend, m, n, k, N, off=0, maxima=False):
+    """The shifts one item's call left in its workspace block (`off` bytes behind the 256-aligned start of `work`), read through gemmul8_get_layout; with
+    maxima (real INT8, accurate mode: the only case in which nothing reuses that scratch afterwards) also the bound GEMM's integer row and column maxima."""
+    base = (work.data_ptr() + 255) // 256 * 256 + off
+    L = g.Layout()
+    g.check(g.lib().gemmul8_get_layout(code, backend, m, n, k, N, base, None, None, 0, 0, C.byref(L)))
+
+    def vec(ptr, count, dt):
+        o = ptr - work.data_ptr()
+        return work[o:o + count * np.dtype(dt).itemsize].cpu().numpy().view(dt).copy()
+    out = dict(sftA=vec(L.sftA, m, np.int16), sftB=vec(L.sftB, n, np.int16))
+    if maxima:
+        out["rowmax"], out["colmax"] = vec(L.scratch, m, np.int32), vec(L.scratch + 4 * L.mp, n, np.int32)
+    return out
+
+
+def _same_bits_nan(a, b):
+    """bit-equal, any NaN matching any NaN (non-finite mode 1)"""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype.kind == "c":
+        rdt = np.float32 if a.dtype.itemsize == 8 else np.float64
+        a, b = a.view(rdt), b.view(rdt)
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint8), b[~nb].view(np.uint8))
+
+
+def batched_views_case(As, Bs, C0s, N, fast, backend=g.INT8, opA="N", opB="N", alpha=1.0, beta=0.0, pad=(0, 0, 0), gap=(0, 0, 0), head=0, mode=0,
+                       oracle_items=None, oracle_shifts=True, maxima=False, what=""):
+    """ONE gemmul8_gemm_batched call on views, and the three checks of tests/test_gpu_batched_paths.py.
+
+    As, Bs, C0s: the items as stored (numpy; `batched_data`), one entry in As / Bs for an operand every item shares (stride 0).  A, B and C live in larger
+    device buffers: ld = rows + pad[i], stride = ld * cols + gap[i] (i = 0, 1, 2 for A, B, C), the first window `head` elements into the buffer.  Outside the
+    windows the C buffer holds C_SENTINEL, the A and B buffers huge finite numbers (mode 1: NaN).  Asserted:
+      (a) every item is bit-identical to a gemmul8_gemm call on the same views (mode 1: any NaN matches any NaN), and so are its shifts in the workspace
+          (with maxima=True also the bound GEMM's integer maxima);
+      (b) the items of `oracle_items` (default: first, middle, last; mode 1: none) are bit-identical to oracle_lib.gemm with the same ops, scalars, C0, mode and
+          backend, fed with the shifts the BATCHED call left in that item's workspace block; for the first of them the oracle's own shifts are held against
+          those (shifts_close: equal but for rare +-1 at the floor boundaries of the device's log2; oracle_shifts=False leaves that run out).  An item whose C0 holds a
+          NaN or an Inf is compared with any NaN matching any NaN;
+      (c) every byte of the C buffer outside the windows, and the whole A and B buffers, are unchanged.
+    Returns {"C": the C buffer after the batched call (numpy), "windows": [m x n numpy per item], "vectors": [work_vectors per item]}."""
+    batch = len(C0s)
+    dt = C0s[0].dtype
+    m, n = C0s[0].shape
+    k = As[0].shape[1] if opA == "N" else As[0].shape[0]
+    assert (Bs[0].shape == (k, n) if opB == "N" else Bs[0].shape == (n, k)) and len(As) in (1, batch) and len(Bs) in (1, batch)
+    if backend == g.FP8:
+        select_fp8_bound_mode(SAFE)
+    cplx = dt.kind == "c"
+    code, esz = ol.DT[dt], dt.itemsize
+    bufA, lda, sA, _ = _strided_buffer(As, batch, pad[0], gap[0], head, _fill_operand(dt, mode == 1))
+    bufB, ldb, sB, _ = _strided_buffer(Bs, batch, pad[1], gap[1], head, _fill_operand(dt, mode == 1))
+    bufC, ldc, sC, inside = _strided_buffer([np.asarray(c) for c in C0s], batch, pad[2], gap[2], head, _fill_c(dt))
+    dA, dB, dC, dC1 = (torch.from_numpy(x.copy()).cuda() for x in (bufA, bufB, bufC, bufC))
+    pA, pB, pC, pC1 = (t.data_ptr() + head * esz for t in (dA, dB, dC, dC1))
+    lib = g.lib()
+    W = lib.gemmul8_batched_item_bytes(int(cplx), backend, m, n, k, N)
+    work = torch.empty(lib.gemmul8_work_size_batched(int(cplx), backend, m, n, k, N, batch), dtype=torch.uint8, device="cuda")
+    work1 = torch.empty(g.work_size(cplx, backend, m, n, k, N)[0], dtype=torch.uint8, device="cuda")
+    al, be = np.array([alpha], dt), np.array([beta], dt)
+    st = torch.cuda.current_stream().cuda_stream
+    what = f"{what} {dt.name} backend={backend} {m}x{n}x{k} batch={batch} N={N} fast={fast} op={opA}{opB} scalars=({alpha}, {beta}) pad={pad} gap={gap} head={head} " \
+           f"strides=({sA}, {sB}, {sC}) mode={mode}"
+    prev = g.set_nonfinite_mode(mode)
+    try:
+        g.check(lib.gemmul8_gemm_batched(st, code, backend, g.OPS[opA], g.OPS[opB], m, n, k, al.ctypes.data, pA, lda, sA, pB, ldb, sB, be.ctypes.data, pC, ldc, sC,
+                                         batch, N, int(fast), work.data_ptr()), "gemmul8_gemm_batched: " + what)
+        torch.cuda.synchronize()
+        vb = [work_vectors(work, code, backend, m, n, k, N, b * W, maxima) for b in range(batch)]
+        v1 = []
+        for b in range(batch):
+            g.check(lib.gemmul8_gemm(st, code, backend, g.OPS[opA], g.OPS[opB], m, n, k, al.ctypes.data, pA + b * sA * esz, lda, pB + b * sB * esz, ldb,
+                                     be.ctypes.data, pC1 + b * sC * esz, ldc, N, int(fast), work1.data_ptr(), None, None, 0, 0, 0, 0, None), "gemmul8_gemm: " + what)
+            torch.cuda.synchronize()
+            v1.append(work_vectors(work1, code, backend, m, n, k, N, 0, maxima))
+    finally:
+        g.set_nonfinite_mode(prev)
+    got, per_item = dC.cpu().numpy(), dC1.cpu().numpy()
+    assert bits_equal(dA.cpu().numpy(), bufA) and bits_equal(dB.cpu().numpy(), bufB), "an operand buffer was written: " + what                         # (c)
+    assert bits_equal(got[~inside], bufC[~inside]), f"{int((got[~inside].view(np.uint8) != bufC[~inside].view(np.uint8)).sum())} bytes of the C buffer outside the windows were written: " + what
+    assert bits_equal(per_item[~inside], bufC[~inside]), "a per-item call wrote outside its window: " + what
+
+    def window(buf, b):
+        return buf[head + b * sC:head + b * sC + ldc * n].reshape(n, ldc)[:, :m].T
+    for b in range(batch):                                                                                                                              # (a)
+        wb, w1 = window(got, b), window(per_item, b)
+        same = _same_bits_nan(wb, w1) if mode == 1 else bits_equal(wb, w1)
+        assert same, f"item {b}: {int((wb != w1).sum())} entries differ from the per-item call (NaN counted): " + what
+        for key in vb[b]:
+            assert np.array_equal(vb[b][key], v1[b][key]), f"item {b}: {key} in the workspace differs from the per-item call's at {np.nonzero(vb[b][key] != v1[b][key])[0][:5]}: " + what
+    if oracle_items is None:
+        oracle_items = sorted({0, batch // 2, batch - 1}) if mode == 0 else ()
+    for i, b in enumerate(oracle_items):                                                                                                                # (b)
+        A, B = As[b if len(As) > 1 else 0], Bs[b if len(Bs) > 1 else 0]
+        kw = dict(fastmode=fast, backend=backend, opA=opA, opB=opB, alpha=alpha, beta=beta, C0=C0s[b])
+        if i == 0 and oracle_shifts:
+            _, ito = ol.gemm(A, B, N, want_intermediates=True, **kw)
+            shifts_close(vb[b]["sftA"], ito["sftA"], f"item {b} sftA"), shifts_close(vb[b]["sftB"], ito["sftB"], f"item {b} sftB")
+        Co = np.asarray(ol.gemm(A, B, N, sftA_in=vb[b]["sftA"], sftB_in=vb[b]["sftB"], **kw))
+        finite_c0 = bool(np.isfinite(C0s[b]).all())
+        assert np.isfinite(Co).all() or not finite_c0, "the oracle's C is not finite: the case's data leaves the type's range: " + what
+        wb = window(got, b)
+        assert bits_equal(wb, Co) if finite_c0 else _same_bits_nan(wb, Co), f"item {b}: {int((wb != Co).sum())} entries differ from the oracle, first at (row, col) {np.argwhere(wb != Co)[:3].tolist()}: " + what
+    return dict(C=got, windows=[window(got, b).copy() for b in range(batch)], vectors=vb)

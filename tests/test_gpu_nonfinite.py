@@ -74,7 +74,11 @@ def flagged_masks(Aop, Bop):
 
 def cmul(a, b):
     """Textbook complex product (componentwise), as the contract states it for s and alpha * s."""
-    return (a.real * b.real - a.imag * b.imag) + 1j * (a.real * b.imag + a.imag * b.real) if np.iscomplexobj(a) else a * b
+    if not np.iscomplexobj(a):
+        return a * b
+    out = np.empty(np.broadcast(a, b).shape, np.result_type(a, b))   # component by component: `re + 1j * im` would turn the real part into NaN (0 * Inf) wherever im is infinite
+    out.real, out.imag = a.real * b.real - a.imag * b.imag, a.real * b.imag + a.imag * b.real
+    return out
 
 
 def expected_flagged(Aop, Bop, fr, fc, alpha, beta, C0):
@@ -87,7 +91,9 @@ def expected_flagged(Aop, Bop, fr, fc, alpha, beta, C0):
         def s_of(Ai, Bj):  # Ai: (r, k), Bj: (k, c) -> sums over k, componentwise textbook products
             if dt.kind == "c":
                 ar, ai, br, bi = Ai.real[:, :, None], Ai.imag[:, :, None], Bj.real[None], Bj.imag[None]
-                return ((ar * br - ai * bi).sum(axis=1) + 1j * (ar * bi + ai * br).sum(axis=1)).astype(dt)
+                s = np.empty((Ai.shape[0], Bj.shape[1]), dt)   # component by component: `re + 1j * im` would turn the real part into NaN (0 * Inf) wherever im is infinite
+                s.real, s.imag = (ar * br - ai * bi).sum(axis=1), (ar * bi + ai * br).sum(axis=1)
+                return s
             return (Ai[:, :, None] * Bj[None]).sum(axis=1).astype(dt)
         S = np.zeros((m, n), dt)
         S[fr, :] = s_of(Aop[fr], Bop)
