@@ -16,6 +16,7 @@ S, D, Cx, Z = 0, 1, 2, 3
 INT8, FP8 = 0, 1
 OPS = {"N": 0, "T": 1, "C": 2}
 UPLO = {"L": 0, "U": 1}
+SIDE = {"L": 0, "R": 1}
 
 
 class Layout(C.Structure):
@@ -36,7 +37,8 @@ _lib = None
 
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
            "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
-           "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk", "gemmul8_syr2k"]
+           "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk", "gemmul8_syr2k",
+           "gemmul8_symm", "gemmul8_hemm"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
 
@@ -127,6 +129,11 @@ def bind(L):
     L.gemmul8_syr2k.restype = C.c_int
     L.gemmul8_syr2k.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    L.gemmul8_symm.restype = C.c_int
+    L.gemmul8_symm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    L.gemmul8_hemm.restype = C.c_int
+    L.gemmul8_hemm.argtypes = L.gemmul8_symm.argtypes
     L.gemmul8_set_fp8_bound_mode.restype = C.c_int
     L.gemmul8_set_fp8_bound_mode.argtypes = [C.c_int]
     L.gemmul8_set_nonfinite_mode.restype = C.c_int
@@ -302,6 +309,55 @@ def syr2k(A, B, num_moduli, uplo="L", trans="N", fastmode=False, alpha=1.0, beta
                              be.ctypes.data, C_out.data_ptr(), C_out.stride(0), num_moduli, int(fastmode), work.data_ptr(), tm)
     check(rc, "gemmul8_syr2k")
     return C_out, (list(tm) if timers else None), work
+
+
+def symm_work_size(is_complex, m, n, side, num_moduli):
+    """Bytes of workspace gemmul8_symm / gemmul8_hemm need: that of the equivalent GEMM, whose inner dimension is the order of A (m for side "L", n for "R")."""
+    return work_size(is_complex, INT8, m, n, m if SIDE[side] == 0 else n, num_moduli)[0]
+
+
+def _symm(name, A, B, num_moduli, side, uplo, fastmode, alpha, beta, C_out, work, stream, timers):
+    import numpy as np
+    import torch
+    dt = A.dtype
+    for X in (A, B):
+        assert X.is_cuda and X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]
+    if B.dtype != dt or A.shape[0] != A.shape[1] or (C_out is not None and (C_out.dtype != dt or C_out.dim() != 2 or C_out.stride(1) != 1)):
+        raise TypeError("A, B and C_out must share one dtype, A must be square, and every column must be contiguous")
+    n, m = B.shape
+    ka = m if SIDE[side] == 0 else n
+    if A.shape[0] != ka:
+        raise ValueError(f"A is of order {A.shape[0]}, side {side!r} of an {m} x {n} B needs {ka}")
+    if C_out is None:
+        C_out = torch.zeros((n, m), dtype=dt, device=A.device)
+    if work is None:
+        work = torch.empty(symm_work_size(dt.is_complex, m, n, side, num_moduli), dtype=torch.uint8, device=A.device)
+    np_dt = {torch.float32: np.float32, torch.float64: np.float64, torch.complex64: np.complex64, torch.complex128: np.complex128}[dt]
+    al = np.array([alpha], dtype=np_dt)
+    be = np.array([beta], dtype=np_dt)
+    tm = (C.c_double * 4)() if timers else None
+    st = stream if stream is not None else torch.cuda.current_stream(A.device).cuda_stream
+    rc = getattr(lib(), name)(st, _dtype_code(dt), INT8, SIDE[side], UPLO[uplo], m, n, al.ctypes.data, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0),
+                              be.ctypes.data, C_out.data_ptr(), C_out.stride(0), num_moduli, int(fastmode), work.data_ptr(), tm)
+    check(rc, name)
+    return C_out, (list(tm) if timers else None), work
+
+
+def symm(A, B, num_moduli, side="L", uplo="L", fastmode=False, alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, timers=False):
+    """C = alpha*A*B + beta*C (side "L", A is m x m) or alpha*B*A + beta*C (side "R", A is n x n) with a SYMMETRIC A of which only the triangle `uplo`
+    ("L" / "U") is read, through gemmul8_symm: INT8 backend, plain transpose for complex types too; bit-identical to
+    `gemm(Afull, B)` (side "L") / `gemm(B, Afull, opB="T")` (side "R") with the full matrix materialised, which this call never does.
+    A, B and C_out are column-major matrices held as tensors of shape (cols, rows), as in `gemm`; views with a larger leading dimension are taken
+    through tensor.stride(0); a fresh C_out is zero-filled.  Returns (C, timers_ns or None, work)."""
+    return _symm("gemmul8_symm", A, B, num_moduli, side, uplo, fastmode, alpha, beta, C_out, work, stream, timers)
+
+
+def hemm(A, B, num_moduli, side="L", uplo="L", fastmode=False, alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, timers=False):
+    """`symm` with a HERMITIAN A through gemmul8_hemm: complex types, complex alpha and beta; the mirrored triangle is the conjugate of the stored one and
+    the imaginary parts of the stored diagonal count as 0.  Bit-identical to `gemm(Afull, B)` (side "L") / `gemm(B, Afull, opB="C")` (side "R")."""
+    if not A.dtype.is_complex:
+        raise TypeError("hemm takes complex64 / complex128 (use symm for the real types)")
+    return _symm("gemmul8_hemm", A, B, num_moduli, side, uplo, fastmode, alpha, beta, C_out, work, stream, timers)
 
 
 def gemm_batched(A, B, num_moduli, fastmode=False, opA="N", opB="N", alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, backend=INT8):

@@ -253,12 +253,18 @@ static int bound_gemm_i8(hipStream_t stream, bool cplx, const gemmul8_layout* L,
     return GEMMUL8_OK;
 }
 
+// gemmul8_symm / gemmul8_hemm: which operand of the equivalent GEMM is in symmetric form (oz2_kernels.h SymForm), passed down from symm() only
+struct SymSide {
+    bool onB;   // false: the A side (side = LEFT), true: the B side (RIGHT)
+    int form;   // kSymLower / kSymUpper
+    bool herm;
+};
 // nf: non-finite mode 1 (gemmul8_set_nonfinite_mode) -- passed down from the whole-call entry points only; the phase-level entry points run mode 0
 // rows from which a row-strided operand takes the one-read extract (16 / 32 rows per workgroup): measured, DESIGN.md 3.4
 constexpr size_t kOneReadMinRows = 8192;
 static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
                            const void* B, size_t ldb, unsigned N, size_t col_begin, size_t col_end, const gemmul8_layout* L, int skipA, int skipB,
-                           bool nf) {
+                           bool nf, const SymSide* sym = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!L || !A || !B) return GEMMUL8_E_ARG;
     if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
@@ -288,6 +294,7 @@ static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int 
     const size_t esz = is_f32(dtype) ? 4 : 8;
     auto one_read = [&](bool run, bool kmaj, size_t rows, const void* X, size_t ld) {
         const bool aligned = ((reinterpret_cast<uintptr_t>(X) | (ld * esz)) & 15u) == 0;
+        if (sym) return false;  // a symmetric-form operand keeps the two-pass form, and its partner shares its launches
         return run && !kmaj && extract_one_read_ok(dtype, backend, L->kp) && (force1 < 0 ? rows >= kOneReadMinRows && aligned : force1 == 1);
     };
     const bool orA = one_read(runA, kmajA, m, A, lda), orB = one_read(runB, kmajB, n, B, ldb);
@@ -304,6 +311,7 @@ static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int 
         eb.one_read = orB;
         if (srB) eb.amax = (char*)amax + (srA ? (size_t)ea.parts * srA * ub : 0), eb.parts = amax_parts_for(n, k, room * srB / (srA + srB) / srB);
     }
+    if (sym) (sym->onB ? eb : ea).sym = sym->form, (sym->onB ? eb : ea).herm = sym->herm;
     if (srA + srB) OZ2_HIP(launch_amax_pair(stream, dtype, k, ea, eb));
     const size_t zero_bytes = 4 * (L->mp + np);
     if (knobs().scale_fold) {
@@ -356,7 +364,7 @@ struct TwinPlanes {
 };
 static int scale_finish_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
                            const void* B, size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end, const gemmul8_layout* L, int skipA,
-                           int skipB, bool nf, const TwinPlanes* twinA = nullptr) {
+                           int skipB, bool nf, const TwinPlanes* twinA = nullptr, const SymSide* sym = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!L || !A || !B) return GEMMUL8_E_ARG;
     if (!moduli_ok(dtype, N) || t_end > N || t_begin > t_end) return GEMMUL8_E_NUM_MODULI;
@@ -374,6 +382,7 @@ static int scale_finish_nf(void* stream_, int dtype, int backend, int op_A, int 
     if (!skipB) ob = QuantOperand{kmajB, conjB, n, B, ldb, L->sftB, (int8_t*)L->B_lo, L->sizeB, L->part_strideB, g_batch.sb, f6 ? n : 0};
     oa.nf = ob.nf = nf;
     if (twinA) oa.lo2 = twinA->lo, oa.plane_stride2 = twinA->plane_stride, oa.part_stride2 = twinA->part_stride;
+    if (sym) (sym->onB ? ob : oa).sym = sym->form, (sym->onB ? ob : oa).herm = sym->herm;
     if (fastmode) {
         OZ2_HIP(launch_fast_shift_pair(stream, dtype, backend, N, k, oa, ob));
         if (nf) {  // flagged rows / columns: sentinel shifts before the quantise reads them
@@ -410,12 +419,12 @@ int gemmul8_scale_finish(void* stream_, int dtype, int backend, int op_A, int op
 
 static int scale_nf(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda, const void* B,
                     size_t ldb, unsigned N, int fastmode, unsigned t_begin, unsigned t_end, const gemmul8_layout* L, int skipA, int skipB, bool nf,
-                    const TwinPlanes* twinA = nullptr) {
+                    const TwinPlanes* twinA = nullptr, const SymSide* sym = nullptr) {
     if (!fastmode) {
-        int rc = scale_bounds_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, 0, n, L, skipA, skipB, nf);
+        int rc = scale_bounds_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, 0, n, L, skipA, skipB, nf, sym);
         if (rc) return rc;
     }
-    return scale_finish_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB, nf, twinA);
+    return scale_finish_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB, nf, twinA, sym);
 }
 
 int gemmul8_scale(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* A, size_t lda,
@@ -819,6 +828,70 @@ int gemmul8_herk(void* stream_, int dtype, int backend, int uplo, int trans, siz
 int gemmul8_syr2k(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda, const void* B,
                   size_t ldb, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
     return rank_k(kSyr2k, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, B, ldb, beta, C, ldc, N, fastmode, work, timers_ns);
+}
+
+// ---- product with a symmetric / Hermitian matrix of which one triangle is stored (no counterpart in the reference).  Afull is never materialised: the
+// call is the equivalent GEMM -- LEFT: (N, N) Afull B, RIGHT: (N, T) / (N, C) B op(Afull) -- whose symmetric operand the scaling kernels read through the
+// triangle (the symmetric form of oz2_scale.hip; row-strided on either side, so the fast mode's round-up sums have one order).  Everything behind the
+// scaling phase is gemmul8_gemm's: the residue GEMMs over the full m x n, the plain CRT, the workspace layout.
+enum SymmKind { kSymm = 0, kHemm = 1 };
+static int symm(int kind, hipStream_t stream, int dtype, int backend, int side, int uplo, size_t m, size_t n, const void* alpha, const void* A, size_t lda,
+                const void* B, size_t ldb, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    const bool herm = kind == kHemm;
+    if (timers_ns) timers_ns[0] = timers_ns[1] = timers_ns[2] = timers_ns[3] = 0.0;
+    if (dtype < 0 || dtype > 3 || backend < 0 || backend > 1) return GEMMUL8_E_ARG;
+    if (herm && !is_complex(dtype)) return GEMMUL8_E_ARG;  // BLAS has no real HEMM
+    if (side == 141) side = GEMMUL8_LEFT;  // hipblasSideMode_t
+    else if (side == 142) side = GEMMUL8_RIGHT;
+    if (uplo == 122) uplo = GEMMUL8_LOWER;  // hipblasFillMode_t
+    else if (uplo == 121) uplo = GEMMUL8_UPPER;
+    if ((side != GEMMUL8_LEFT && side != GEMMUL8_RIGHT) || (uplo != GEMMUL8_LOWER && uplo != GEMMUL8_UPPER)) return GEMMUL8_E_ARG;
+    if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
+    if (!alpha || !beta || !A || !B || !C || !work) return GEMMUL8_E_ARG;
+    const size_t ka = side == GEMMUL8_LEFT ? m : n;
+    if (ka > (size_t(1) << 17)) return GEMMUL8_E_ARG;
+    if (backend == kFP8) return GEMMUL8_E_UNSUPPORTED;  // the FP6 panel writer has no symmetric form
+    if (m == 0 || n == 0) return GEMMUL8_OK;
+    gemmul8_layout L;
+    int rc = gemmul8_get_layout(dtype, backend, m, n, ka, N, work, nullptr, nullptr, 0, 0, &L);
+    if (rc) return rc;
+    Timer* T = timers_ns ? thread_timer() : nullptr;
+    if (T && hipEventRecord(T->ev[0], stream) != hipSuccess) {
+        (void)hipGetLastError();
+        T = nullptr;
+    }
+    const SymSide sym{side == GEMMUL8_RIGHT, uplo == GEMMUL8_LOWER ? kSymLower : kSymUpper, herm};
+    if (side == GEMMUL8_LEFT) rc = scale_nf(stream, dtype, backend, 0, 0, m, n, ka, A, lda, B, ldb, N, fastmode, 0, N, &L, 0, 0, false, nullptr, &sym);
+    else rc = scale_nf(stream, dtype, backend, 0, herm ? 2 : 1, m, n, ka, B, ldb, A, lda, N, fastmode, 0, N, &L, 0, 0, false, nullptr, &sym);
+    if (rc) return rc;
+    if (T) OZ2_HIP(hipEventRecord(T->ev[1], stream));
+    rc = gemmul8_lowprec_gemm(stream, dtype, backend, m, n, ka, N, 0, N, &L);
+    if (rc) return rc;
+    if (T) OZ2_HIP(hipEventRecord(T->ev[2], stream));
+    rc = gemmul8_crt(stream, dtype, backend, N, m, n, L.C_mid, L.mp, L.sizeC, L.sftA, L.sftB, alpha, beta, C, ldc);
+    if (rc) return rc;
+    if (T) {
+        OZ2_HIP(hipEventRecord(T->ev[3], stream));
+        OZ2_HIP(hipEventSynchronize(T->ev[3]));
+        float ms;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[0], T->ev[1]));
+        timers_ns[0] = ms * 1e6;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[1], T->ev[2]));
+        timers_ns[1] = ms * 1e6;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[2], T->ev[3]));
+        timers_ns[3] = ms * 1e6;
+    }
+    return GEMMUL8_OK;
+}
+
+int gemmul8_symm(void* stream_, int dtype, int backend, int side, int uplo, size_t m, size_t n, const void* alpha, const void* A, size_t lda, const void* B,
+                 size_t ldb, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    return symm(kSymm, (hipStream_t)stream_, dtype, backend, side, uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc, N, fastmode, work, timers_ns);
+}
+
+int gemmul8_hemm(void* stream_, int dtype, int backend, int side, int uplo, size_t m, size_t n, const void* alpha, const void* A, size_t lda, const void* B,
+                 size_t ldb, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    return symm(kHemm, (hipStream_t)stream_, dtype, backend, side, uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc, N, fastmode, work, timers_ns);
 }
 
 int gemmul8_add_f64(void* stream_, double* dst, const double* src, size_t count) {

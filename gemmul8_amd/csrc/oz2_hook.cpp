@@ -12,6 +12,8 @@
 //   hipblas{S,D,C,Z}syrk(_64), hipblas{C,Z}herk(_64)                        yes: one triangle through gemmul8_syrk / gemmul8_herk (INT8 backend, k <= 2^17; HERK: real
 //                                                                             alpha / beta, N / C only); everything else is the native routine's, see try_syrk_impl
 //   hipblas{S,D,C,Z}syr2k(_64)                                              yes: one triangle through gemmul8_syr2k (INT8 backend, k <= 2^16, N / T only); see try_syrk_impl
+//   hipblas{S,D,C,Z}symm(_64), hipblas{C,Z}hemm(_64)                        yes: the product with a symmetric / Hermitian matrix through gemmul8_symm / gemmul8_hemm (INT8 backend,
+//                                                                             order of A <= 2^17; one triangle of A read in place); see try_symm_impl
 //   hipblasLtMatmul, hipblasLtDestroy                                       yes (PyTorch's float32 matmuls): the plain case only, see lt_try
 //   hipblasLtMatrixLayoutCreate / SetAttribute / Destroy                    yes: record what a layout holds (hipBLASLt cannot be asked)
 //   rocblas_{s,d,c,z}gemm, rocblas_{s,d,c,z}gemm_strided_batched,           yes, only with GEMMUL8_HOOK_ROCBLAS=1: applications that call rocBLAS directly
@@ -30,7 +32,7 @@
 //  the rest is this build's only:
 //   GEMMUL8_FP8_BOUND, GEMMUL8_NONFINITE
 //                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace); under `ieee` SYRK / HERK / SYR2K
-//                                              calls are not emulated (try_syrk_impl)
+//                                              calls are not emulated (try_syrk_impl), nor are SYMM / HEMM calls (try_symm_impl)
 //   GEMMUL8_MIN_FLOPS              per call    unset or 0 = emulate every selected call (the reference's behaviour); `auto` = a fitted cost model decides
 //                                              per call (below_floor); a number = floor on 2*m*n*k.  The first call a floor declines is logged once.
 //   GEMMUL8_DIST                   per call    blocks | moduli | fp64sum: shard every emulated GEMM over the ranks of an SPMD job (try_dist)
@@ -39,7 +41,8 @@
 //   GEMMUL8_HOOK_ROCBLAS           per call    "1" = the rocBLAS entry points above act
 //   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
 //   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call);
-//                                              a line each for hipblas{S,D,C,Z}syrk, hipblas{C,Z}herk and hipblas{S,D,C,Z}syr2k when one was seen
+//                                              a line each for hipblas{S,D,C,Z}syrk, hipblas{C,Z}herk, hipblas{S,D,C,Z}syr2k, hipblas{S,D,C,Z}symm and
+//                                              hipblas{C,Z}hemm when one was seen
 //   GEMMUL8_HOOK_VERBOSE           per call    "1" = say why a hipblasLtMatmul call was left to the native routine
 //
 // Per-handle state under a mutex: three grow-only stream-ordered buffers (hipMallocAsync / hipFreeAsync), event hand-off when the handle's
@@ -66,13 +69,13 @@
 
 // The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
 // `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
-// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k: every SYRK / HERK / SYR2K call then goes to the native routine); the shim, which binds to this
+// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_symm / gemmul8_hemm: every such call then goes to the native routine); the shim, which binds to this
 // project's own libgemmul8.so, requires every entry.
 #define OZ2_ABI(X)                                                                                          \
     X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
     X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
     X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak))) X(herk, __attribute__((weak))) \
-    X(syr2k, __attribute__((weak)))
+    X(syr2k, __attribute__((weak))) X(symm, __attribute__((weak))) X(hemm, __attribute__((weak)))
 #ifndef OZ2_HOOK_SHIM
 #define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
 OZ2_ABI(X)
@@ -562,6 +565,8 @@ struct HookStats {
     std::atomic<unsigned long long> emu_mflops{0}, nat_mflops{0};  // 2 m n k batch / 1e6 (x 4 for complex), rounded down
     // hipblas?syrk [0] / hipblas?herk [1] / hipblas?syr2k [2]: n (n + 1) k / 1e6 (x 4; syr2k: x 2)
     std::atomic<unsigned long long> emu_syrk[3] = {{0}, {0}, {0}}, nat_syrk[3] = {{0}, {0}, {0}}, emu_syrk_mflops[3] = {{0}, {0}, {0}}, nat_syrk_mflops[3] = {{0}, {0}, {0}};
+    // hipblas?symm [0] / hipblas?hemm [1]: 2 m n ka / 1e6 (x 4 for complex)
+    std::atomic<unsigned long long> emu_symm[2] = {{0}, {0}}, nat_symm[2] = {{0}, {0}}, emu_symm_mflops[2] = {{0}, {0}}, nat_symm_mflops[2] = {{0}, {0}};
     static void dump();
     HookStats() { std::atexit(&HookStats::dump); }
 };
@@ -579,6 +584,12 @@ void HookStats::dump() {
             std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu %s calls (%.3f TFLOP), native %llu %s calls through the hooked entry points (%.3f TFLOP)\n",
                          h.emu_syrk[kind].load(), kRankName[kind], h.emu_syrk_mflops[kind].load() * 1e-6, h.nat_syrk[kind].load(), kRankName[kind],
                          h.nat_syrk_mflops[kind].load() * 1e-6);
+    static const char* const kSymmName[2] = {"SYMM", "HEMM"};
+    for (int kind = 0; kind < 2; ++kind)
+        if (h.emu_symm[kind].load() + h.nat_symm[kind].load())
+            std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu %s calls (%.3f TFLOP), native %llu %s calls through the hooked entry points (%.3f TFLOP)\n",
+                         h.emu_symm[kind].load(), kSymmName[kind], h.emu_symm_mflops[kind].load() * 1e-6, h.nat_symm[kind].load(), kSymmName[kind],
+                         h.nat_symm_mflops[kind].load() * 1e-6);
 }
 void count_call(bool emulated, const GemmCall& c) {
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
@@ -808,6 +819,102 @@ bool try_syrk(int kind, hipblasHandle_t handle, int dtype, int uplo, int trans, 
         const unsigned long long mf = (unsigned long long)((double)n * ((double)n + 1.0) * (double)k * (dtype >= 2 ? 4.0 : 1.0) * (kind == kSYR2K ? 2.0 : 1.0) * 1e-6);
         (served ? h.emu_syrk : h.nat_syrk)[kind].fetch_add(1, std::memory_order_relaxed);
         (served ? h.emu_syrk_mflops : h.nat_syrk_mflops)[kind].fetch_add(mf, std::memory_order_relaxed);
+    }
+    return served;
+}
+
+// ---- hipblas{S,D,C,Z}symm and hipblas{C,Z}hemm (and the _64 twins): C = alpha A B + beta C / alpha B A + beta C with a symmetric / Hermitian A of which one
+// triangle is stored, through gemmul8_symm / gemmul8_hemm (no counterpart in the reference).  ka = the order of A (m for side = left, n for right).
+// Selection: the type's GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, ka > 2^17, a moduli count outside the
+// type's range, GEMMUL8_NONFINITE=ieee (each said once per routine), a side or fill mode other than left / right and upper / lower, a dimension an int
+// cannot hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: a number is a floor on 2 m n ka, `auto` takes the GEMM model's decision for
+// (m, n, ka).  GEMMUL8_DIST and the skip-scaling switches do not apply.  The workspace (the equivalent GEMM's) grows through wC, as for SYRK.
+enum { kSYMM = 0, kHEMM = 1 };
+bool symm_below_floor(int kind, int dtype, double m, double n, double ka, unsigned N, bool fast) {
+    const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
+    if (!s || !*s) return false;
+    bool declined;
+    if (s[0] == 'a' || s[0] == 'A') {
+        declined = floor_model_declines(dtype, m, n, ka, N, fast, GEMMUL8_INT8, 1.0);
+    } else {
+        const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
+        declined = f && 2.0 * m * n * ka < (double)f;
+    }
+    if (declined) {
+        static std::once_flag told[2];
+        std::call_once(told[kind], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %c%s m = %.0f, n = %.0f, order of A = %.0f (%u moduli) stays on the native routine -- calls "
+                                 "below the floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], kind == kHEMM ? "HEMM" : "SYMM", m, n, ka, N);
+        });
+    }
+    return declined;
+}
+bool try_symm_impl(int kind, hipblasHandle_t handle, int dtype, int side, int uplo, int m, int n, const void* alpha, const void* A, int lda, const void* B,
+                   int ldb, const void* beta, void* C, int ldc, hipblasStatus_t* status) {
+    if (!(kind == kHEMM ? (bool)abi().hemm : (bool)abi().symm)) return false;
+    const char* const name = kind == kHEMM ? "HEMM" : "SYMM";
+    if ((side != HIPBLAS_SIDE_LEFT && side != HIPBLAS_SIDE_RIGHT) || (uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER)) return false;
+    const int ka = side == HIPBLAS_SIDE_LEFT ? m : n;
+    Selection s;
+    if (!selection_from_env(dtype, &s)) {
+        if (s.N != 0) {
+            static std::once_flag told[2];
+            std::call_once(told[kind], [&] {
+                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %c%s calls use the native routine\n", kTypes[dtype].nmod, s.N,
+                             kTypes[dtype].max_moduli, "SDCZ"[dtype], name);
+            });
+        }
+        return false;
+    }
+    if (s.backend == GEMMUL8_FP8 || ka > kMaxK) {
+        static std::once_flag told[2][2];  // the backend, the order of A: one notice each
+        std::call_once(told[kind][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for an A of order <= %d only (GEMMUL8_BACKEND=%d, order %d): using the native "
+                                 "routine for such calls\n", name, kMaxK, s.backend, ka);
+        });
+        return false;
+    }
+    if (nonfinite_ieee()) {  // gemmul8_symm / hemm ignore the non-finite mode: a NaN or Inf operand would come back as finite numbers
+        static std::once_flag told[2];
+        std::call_once(told[kind], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: %s has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
+                                 "for such calls\n", name);
+        });
+        return false;
+    }
+    if (symm_below_floor(kind, dtype, (double)m, (double)n, (double)ka, s.N, s.fast)) return false;
+    LockedState l = lock_ordered(handle, nullptr);
+    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
+    const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)m, (size_t)n, (size_t)ka, s.N, 0, 0, nullptr, nullptr);
+    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, kind == kHEMM ? "workC (hemm)" : "workC (symm)"); st != HIPBLAS_STATUS_SUCCESS)
+        return *status = st, true;
+    const int rc = (kind == kHEMM ? abi().hemm : abi().symm)(l.stream, dtype, GEMMUL8_INT8, side, uplo, (size_t)m, (size_t)n, alpha, A, (size_t)lda, B, (size_t)ldb,
+                                                             beta, C, (size_t)ldc, s.N, s.fast, l.sp->wC.ptr, nullptr);
+    if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
+        static std::once_flag warned[2];
+        std::call_once(warned[kind], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a %s call (status %d; type %d, m=%d n=%d): using the native routine for such calls\n", name, rc,
+                         dtype, m, n);
+        });
+        return false;
+    }
+    return *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR, true;
+}
+// counted front end; false = the native routine takes the call: also an empty product, a null pointer (the native routine reports it) or a
+// dimension an int cannot hold
+bool try_symm(int kind, hipblasHandle_t handle, int dtype, int side, int uplo, int64_t m, int64_t n, const void* alpha, const void* A, int64_t lda,
+              const void* B, int64_t ldb, const void* beta, void* C, int64_t ldc, hipblasStatus_t* status) {
+    if (tl_native_depth > 0) return false;
+    const int64_t lim = 2147483647;
+    if (m <= 0 || n <= 0 || !alpha || !beta || !A || !B || !C || m > lim || n > lim || lda > lim || ldb > lim || ldc > lim) return false;
+    const bool served = try_symm_impl(kind, handle, dtype, side, uplo, (int)m, (int)n, alpha, A, (int)lda, B, (int)ldb, beta, C, (int)ldc, status);
+    static const bool on = env_one("GEMMUL8_HOOK_STATS");
+    if (on) {
+        HookStats& h = hook_stats();
+        const double ka = side == HIPBLAS_SIDE_RIGHT ? (double)n : (double)m;
+        const unsigned long long mf = (unsigned long long)(2.0 * (double)m * (double)n * ka * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
+        (served ? h.emu_symm : h.nat_symm)[kind].fetch_add(1, std::memory_order_relaxed);
+        (served ? h.emu_symm_mflops : h.nat_symm_mflops)[kind].fetch_add(mf, std::memory_order_relaxed);
     }
     return served;
 }
@@ -1258,6 +1365,14 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
         if (try_syrk(kSYR2K, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;          \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc);              \
     }
+// hipblas{S,D,C,Z}symm (KIND = kSYMM) and hipblas{C,Z}hemm (kHEMM): one signature
+#define OZ2_SYMM_HOOK(NAME, KIND, T, I, CODE)                                                                                           \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasSideMode_t side, hipblasFillMode_t uplo, I m, I n, const T* alpha, const T* A,  \
+                         I lda, const T* B, I ldb, const T* beta, T* C, I ldc) {                                                        \
+        hipblasStatus_t st;                                                                                                             \
+        if (try_symm(KIND, handle, CODE, (int)side, (int)uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;              \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc);                \
+    }
 // hipblas{C,Z}herk: R = the real type of alpha and beta
 #define OZ2_HERK_HOOK(NAME, T, R, I, CODE)                                                                                              \
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const R* alpha, const T* A, \
@@ -1275,6 +1390,8 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     OZ2_SYRK_HOOK(hipblas##U##syrk_64, T, int64_t, CODE)                                                                                \
     OZ2_SYR2K_HOOK(hipblas##U##syr2k, T, int, CODE)                                                                                     \
     OZ2_SYR2K_HOOK(hipblas##U##syr2k_64, T, int64_t, CODE)                                                                              \
+    OZ2_SYMM_HOOK(hipblas##U##symm, kSYMM, T, int, CODE)                                                                                \
+    OZ2_SYMM_HOOK(hipblas##U##symm_64, kSYMM, T, int64_t, CODE)                                                                         \
     OZ2_ROCBLAS_HOOK(rocblas_##L##gemm, rocblas_##L##gemm_strided_batched, T, CODE)                                                     \
     OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_##L##_32, T, int, CODE,                                                                        \
                          "_Z30rocblas_internal_gemm_templateI" TAG "E15rocblas_status_P15_rocblas_handle18rocblas_operation_" Z         \
@@ -1290,6 +1407,10 @@ OZ2_HERK_HOOK(hipblasCherk, hipComplex, float, int, GEMMUL8_C)
 OZ2_HERK_HOOK(hipblasCherk_64, hipComplex, float, int64_t, GEMMUL8_C)
 OZ2_HERK_HOOK(hipblasZherk, hipDoubleComplex, double, int, GEMMUL8_Z)
 OZ2_HERK_HOOK(hipblasZherk_64, hipDoubleComplex, double, int64_t, GEMMUL8_Z)
+OZ2_SYMM_HOOK(hipblasChemm, kHEMM, hipComplex, int, GEMMUL8_C)
+OZ2_SYMM_HOOK(hipblasChemm_64, kHEMM, hipComplex, int64_t, GEMMUL8_C)
+OZ2_SYMM_HOOK(hipblasZhemm, kHEMM, hipDoubleComplex, int, GEMMUL8_Z)
+OZ2_SYMM_HOOK(hipblasZhemm_64, kHEMM, hipDoubleComplex, int64_t, GEMMUL8_Z)
 OZ2_GEMM_EX_HOOK(hipblasGemmEx, int)
 OZ2_GEMM_EX_HOOK(hipblasGemmEx_64, int64_t)
 OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags, int, flags)
@@ -1299,6 +1420,7 @@ OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
 #undef OZ2_ROCBLAS_HOOK
 #undef OZ2_GEMM_EX_HOOK
 #undef OZ2_HERK_HOOK
+#undef OZ2_SYMM_HOOK
 #undef OZ2_SYR2K_HOOK
 #undef OZ2_SYRK_HOOK
 #undef OZ2_SB_HOOK

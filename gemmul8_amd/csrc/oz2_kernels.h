@@ -69,6 +69,11 @@ hipError_t launch_gemm_f8_bound_cplx(hipStream_t stream, int stage, const int8_t
 // zero `bytes` (a multiple of 4, 4-byte aligned) with a kernel: hipMemsetAsync nodes misbehave under HIP-graph replay on ROCm 7.2
 // (tests/test_gpu_graph.py), and a kernel launch is cheaper on the host than the runtime's memset path
 hipError_t launch_zero(hipStream_t stream, void* p, size_t bytes);
+// gemmul8_symm / gemmul8_hemm: an operand in SYMMETRIC FORM has rows == k and its logical element (r, kk) is Afull(r, kk), the matrix BLAS defines from ONE
+// stored triangle of a column-major array X: kSymLower: X[kk*ld + r] where r >= kk, else the mirrored X[r*ld + kk]; kSymUpper: X[kk*ld + r] where r <= kk,
+// else X[r*ld + kk].  herm: the mirrored half is conjugated and the stored diagonal's imaginary part counts as 0.  No element of the other strict
+// triangle is read.  Such an operand enters the kernels as a row-strided one (kmajor == false); INT8 planes, mode 0, a single GEMM.
+enum SymForm { kSymNone = 0, kSymLower = 1, kSymUpper = 2 };
 // one operand of the accurate mode's extract launches; rows == 0 = absent (skip-scaling)
 struct ExtractOperand {
     bool kmajor = false, conj = false;
@@ -84,6 +89,8 @@ struct ExtractOperand {
     unsigned parts = 1;
     size_t pstride = 0;
     bool one_read = false;     // row-strided operand: row maxima and bound plane from one read (no amax_pair_kernel pass, `amax` unused); needs extract_one_read_ok
+    int sym = kSymNone;        // symmetric form (SymForm); keeps the two-pass form (not one_read)
+    bool herm = false;
 };
 bool extract_one_read_ok(int dtype, int backend, size_t kp);  // the one-read form exists: real types, INT8 planes, a single GEMM, kp <= 8192
 unsigned amax_parts_for(size_t rows, size_t k, size_t max_parts);
@@ -113,6 +120,8 @@ struct QuantOperand {
     // Re + Im plane sets (the residues of -Im and Re - Im) to parts 1 and 2 of a second plane array with these strides; its part 0 is not written
     int8_t* lo2 = nullptr;
     size_t plane_stride2 = 0, part_stride2 = 0;
+    int sym = kSymNone;  // symmetric form (SymForm): the launches that carry such an operand are the *_sym_pair kernels of oz2_scale.hip
+    bool herm = false;
 };
 // FP8 backend: the residue planes are FP6 panel images whenever B's last row block fits its share of the reference's plane size
 // (16-row granules at 3/4 byte per element: n >= 45; 64 keeps whole wave tiles); GEMMUL8_FP8_PLANES=e4m3 keeps the e4m3 byte planes

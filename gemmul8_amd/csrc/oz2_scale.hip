@@ -1464,7 +1464,16 @@ template <typename T> static hipError_t launch_amax_pair_t(hipStream_t stream, s
     hipLaunchKernelGGL(amax_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, k, g_batch.ws);
     return hipGetLastError();
 }
+// an operand in symmetric form (ExtractOperand::sym / QuantOperand::sym): the *_sym_pair launches at the end of this file
+static hipError_t launch_amax_sym_pair(hipStream_t stream, int dtype, size_t k, const ExtractOperand& A, const ExtractOperand& B);
+static hipError_t launch_extract_sym_pair(hipStream_t stream, int dtype, int backend, size_t k, size_t kp, const ExtractOperand& A, const ExtractOperand& B,
+                                          void* zero_p, size_t zero_bytes);
+static hipError_t launch_fast_shift_sym_pair(hipStream_t stream, int dtype, int backend, unsigned N, size_t k, const QuantOperand& A, const QuantOperand& B);
+static hipError_t launch_quantise_sym_pair(hipStream_t stream, int dtype, int backend, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A,
+                                           const QuantOperand& B);
+
 hipError_t launch_amax_pair(hipStream_t stream, int dtype, size_t k, const ExtractOperand& A, const ExtractOperand& B) {
+    if (A.sym || B.sym) return launch_amax_sym_pair(stream, dtype, k, A, B);
     switch (dtype) {
     case kF32: return launch_amax_pair_t<float>(stream, k, A, B);
     case kF64: return launch_amax_pair_t<double>(stream, k, A, B);
@@ -1498,6 +1507,7 @@ bool extract_one_read_ok(int dtype, int backend, size_t kp) {
 // extract of both operands (rows == 0: absent) in ONE launch; zero_p / zero_bytes: words the launch also zero-fills (the bound GEMM's maxima arrays)
 hipError_t launch_extract_pair(hipStream_t stream, int dtype, int backend, size_t k, size_t kp, const ExtractOperand& A, const ExtractOperand& B, void* zero_p,
                                size_t zero_bytes) {
+    if (A.sym || B.sym) return launch_extract_sym_pair(stream, dtype, backend, k, kp, A, B, zero_p, zero_bytes);
     const StageArgs a = extract_args(backend, k, kp, A), b = extract_args(backend, k, kp, B);
     auto form = [&](const ExtractOperand& o) { return o.kmajor ? FORM_KMAJOR : o.one_read ? FORM_PANEL : FORM_STRIDED; };
     if ((A.one_read || B.one_read) && !extract_one_read_ok(dtype, backend, kp)) return hipErrorInvalidValue;
@@ -1606,6 +1616,7 @@ hipError_t launch_quantise_seg2(hipStream_t stream, int dtype, int t_begin, int 
 hipError_t launch_quantise_pair(hipStream_t stream, int dtype, int backend, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A,
                                 const QuantOperand& B) {
     if ((A.rows == 0 && B.rows == 0) || t_end <= t_begin) return hipSuccess;
+    if (A.sym || B.sym) return launch_quantise_sym_pair(stream, dtype, backend, t_begin, t_end, k, kp, A, B);
     if (A.lo2 || B.lo2) {  // the twin form: A alone, complex, INT8 byte planes, mode 0
         if (B.rows || B.lo2 || A.rows == 0 || !is_complex(dtype) || backend != kINT8 || A.f6_rows || A.nf) return hipErrorInvalidValue;
         return launch_quantise_twin(stream, dtype, t_begin, t_end, k, kp, A);
@@ -1877,6 +1888,7 @@ template <typename T> __global__ void __launch_bounds__(256) fast_shift_seg2_ker
 
 hipError_t launch_fast_shift_pair(hipStream_t stream, int dtype, int backend, unsigned N, size_t k, const QuantOperand& A, const QuantOperand& B) {
     if (A.rows == 0 && B.rows == 0) return hipSuccess;
+    if (A.sym || B.sym) return launch_fast_shift_sym_pair(stream, dtype, backend, N, k, A, B);
     const float log2P = backend == kINT8 ? GEMMUL8_LOG2P_INT8[N - 2] : GEMMUL8_LOG2P_FP8[N - 2];
     const size_t rpb = 8 * (16 / (is_f32(dtype) ? 4 : 8) / (is_complex(dtype) ? 2 : 1));  // rows per workgroup of the row-strided form
     auto operand = [&](const QuantOperand& o) {
@@ -1909,6 +1921,484 @@ hipError_t launch_fast_shift_seg2(hipStream_t stream, int dtype, unsigned N, siz
     case kF64: hipLaunchKernelGGL(fast_shift_seg2_kernel<double>, grid, dim3(256), 0, stream, a, b, k, log2P); break;
     case kC32: hipLaunchKernelGGL(fast_shift_seg2_kernel<float2>, grid, dim3(256), 0, stream, a, b, k, log2P); break;
     case kC64: hipLaunchKernelGGL(fast_shift_seg2_kernel<double2>, grid, dim3(256), 0, stream, a, b, k, log2P); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ symmetric form (gemmul8_symm / gemmul8_hemm; SymForm in oz2_kernels.h)
+// The operand is Afull, the ka x ka matrix BLAS defines from ONE stored triangle of X, and it enters the scaling as a row-strided operand with rows == k == ka:
+// logical element (r, kk) lies at X[kk*ld + r] on the stored side of the diagonal and at X[r*ld + kk] on the mirrored side (HEMM: conjugated there, and the
+// diagonal's imaginary part counts as 0).  Afull is never materialised and no element of the other strict triangle is read.  Every kernel here is element-wise
+// the strided form's (same bytes given the same values); the fast mode's round-up sums keep fast_shift_strided_body's order.  A general operand that shares a
+// launch with the symmetric one takes its usual body (K-major) or the symmetric body with sym == kSymNone (row-strided: every tile is a stored tile, loaded
+// as stage_strided_body loads it) -- one LDS tile per kernel.
+struct SymStageArgs : StageArgs {
+    int sym;   // SymForm
+    int herm;  // complex types: mirrored half conjugated, real diagonal
+};
+static_assert(2 * sizeof(SymStageArgs) + 16 <= 4096, "two argument blocks must fit the 4 KiB kernel-argument segment");
+
+template <typename T> __device__ __forceinline__ T sym_conj(T v) {
+    if constexpr (ET<T>::cplx) v.y = -v.y;
+    return v;
+}
+// the address rule: logical element (r, kk) of the operand (sym == kSymNone: the plain row-strided element)
+template <typename T> __device__ __forceinline__ T sym_at(const T* X, size_t ld, size_t r, size_t kk, int sym, int herm) {
+    const bool stored = sym == kSymNone || (sym == kSymLower ? r >= kk : r <= kk);
+    T v = stored ? X[kk * ld + r] : X[r * ld + kk];
+    if constexpr (ET<T>::cplx) {
+        if (herm) {
+            if (!stored) v.y = -v.y;
+            if (r == kk) v.y = 0;  // whatever the memory holds
+        }
+    }
+    return v;
+}
+
+// Row-strided staging (the LDS tile and the emit pass of stage_strided_body) with one of three loaders per tile, chosen uniformly for the workgroup:
+//   stored    tile strictly on the stored side of the diagonal: stage_strided_body's loads, 16 bytes down the columns;
+//   mirrored  tile strictly on the other side: its rows are contiguous along kk at X[r*ld + kk] -- 16-byte loads along kk straight into the tile rows
+//             (four per thread, all in flight), conjugated for HEMM; no column-strided scalar loads;
+//   diagonal  a tile the diagonal crosses (at most 128 / TR + 1 row tiles per k tile): the address per element.
+// Scalar loads where the base or ld is not 16-byte aligned; rows and columns past ka read as zero.
+template <typename T, int MODE> __device__ __forceinline__ void stage_sym_body(const SymStageArgs& a, const unsigned bid) {
+    using E = ET<T>;
+    using U = typename E::U;
+    constexpr int TR = StageTile<T>::TR, TK = StageTile<T>::TK;
+    constexpr int PITCH = TK + (sizeof(T) >= 16 ? 1 : 16 / sizeof(T));  // rows stay 16-B aligned
+    constexpr int CH = TK / 4;                                          // 4-wide k chunks per row
+    constexpr int RPP = 256 / CH;                                       // rows per pass
+    __shared__ __attribute__((aligned(16))) T tile[TR][PITCH];
+    using UBm = typename std::conditional<sizeof(U) == 8, unsigned long long, unsigned>::type;
+    [[maybe_unused]] __shared__ UBm rowam[TR];
+    typedef unsigned V4 __attribute__((ext_vector_type(4)));
+    const unsigned nrt = (unsigned)((a.rows + TR - 1) / TR);
+    const unsigned kt = bid / nrt, rt = bid - kt * nrt;  // the row-tile index is the fast one, as in stage_strided_body
+    const size_t r0 = (size_t)rt * TR, kb = (size_t)kt * TK;
+    const T* const X = (const T*)((const char*)a.X + OZ2_ZX);
+    const size_t ld = a.ld;
+    enum { TILE_STORED = 0, TILE_MIRRORED = 1, TILE_DIAGONAL = 2 };
+    int cls = TILE_STORED;
+    if (a.sym != kSymNone) {  // (uniform)
+        const bool above = r0 + TR - 1 < kb, below = r0 > kb + TK - 1;  // every r < every kk / every r > every kk of the tile
+        const bool lower = a.sym == kSymLower;
+        cls = (lower ? below : above) ? TILE_STORED : (lower ? above : below) ? TILE_MIRRORED : TILE_DIAGONAL;
+    }
+    if constexpr (MODE == MODE_BOUND) {  // row maxima of the tile's rows = the maximum over the k splits' partial arrays (amax_sym_pair_kernel)
+        constexpr int PL = 256 / TR;
+        const int rr = threadIdx.x / PL, pp = threadIdx.x % PL;
+        UBm v = 0;
+        if (r0 + rr < a.rows) {
+            const UBm* am = (const UBm*)((const char*)a.amax + OZ2_ZW) + r0 + rr;
+            for (unsigned q = pp; q < a.amax_parts; q += PL) {
+                const UBm w = am[(size_t)q * a.amax_pstride];
+                v = w > v ? w : v;
+            }
+        }
+#pragma unroll
+        for (int d = PL / 2; d >= 1; d >>= 1) {
+            const UBm w = __shfl_xor(v, d);
+            v = w > v ? w : v;
+        }
+        if (pp == 0) rowam[rr] = v;
+    }
+    if (cls == TILE_MIRRORED) {
+        constexpr int EPV = sizeof(T) >= 16 ? 1 : 16 / (int)sizeof(T);  // elements per 16-byte piece
+        constexpr int VPR = TK / EPV;                                   // pieces per tile row
+        constexpr int NV = TR * VPR / 256;                              // pieces per thread (4 for every type)
+        static_assert(NV * 256 == TR * VPR && EPV * sizeof(T) == 16, "tile = whole 16-byte pieces per thread");
+        const bool vec_ok = ((reinterpret_cast<uintptr_t>(X) | (ld * sizeof(T))) & 15u) == 0;
+        V4 buf[NV];
+#pragma unroll
+        for (int it = 0; it < NV; ++it) {
+            const int idx = (int)threadIdx.x + 256 * it;
+            const size_t row = r0 + idx / VPR, kg = kb + (size_t)(idx % VPR) * EPV;
+            V4 v = {0u, 0u, 0u, 0u};
+            if (row < a.rows && kg < a.k) {
+                const T* p = X + row * ld + kg;
+                if (vec_ok && kg + EPV <= a.k) {
+                    v = __builtin_nontemporal_load((const V4*)p);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < EPV; ++e) {
+                        const T t = (kg + e < a.k) ? p[e] : E::zero();
+                        __builtin_memcpy((char*)&v + e * sizeof(T), &t, sizeof(T));
+                    }
+                }
+            }
+            buf[it] = v;
+        }
+#pragma unroll
+        for (int it = 0; it < NV; ++it) {
+            const int idx = (int)threadIdx.x + 256 * it;
+            if constexpr (E::cplx) {
+                if (a.herm) {  // (uniform)
+                    T t[EPV];
+                    __builtin_memcpy(t, &buf[it], 16);
+#pragma unroll
+                    for (int e = 0; e < EPV; ++e) t[e] = sym_conj(t[e]);
+                    __builtin_memcpy(&buf[it], t, 16);
+                }
+            }
+            *(V4*)&tile[idx / VPR][(idx % VPR) * EPV] = buf[it];
+        }
+    } else if (cls == TILE_DIAGONAL) {
+        constexpr int KY = 256 / TR;  // k values fetched per pass
+        const int rx = threadIdx.x % TR, ky = threadIdx.x / TR;
+        const size_t row = r0 + rx;
+#pragma unroll 4
+        for (int it = 0; it < TK / KY; ++it) {
+            const int kk = ky + KY * it;
+            const size_t kg = kb + kk;
+            tile[rx][kk] = (row < a.rows && kg < a.k) ? sym_at<T>(X, ld, row, kg, a.sym, a.herm) : E::zero();
+        }
+    } else if constexpr (sizeof(T) <= 8) {  // stored: the loads of stage_strided_body
+        constexpr int RPL = 16 / (int)sizeof(T);
+        constexpr int RP = TR / RPL;     // row groups per column
+        constexpr int KY = 256 / RP;     // k values fetched per pass
+        const int rp = threadIdx.x % RP, ky = threadIdx.x / RP;
+        const size_t row = r0 + RPL * rp;
+        const T* x = X + row;
+        const bool pair_ok = row + RPL - 1 < a.rows && ((reinterpret_cast<uintptr_t>(x) | (ld * sizeof(T))) & 15u) == 0;
+        V4 buf[TK / KY];
+#pragma unroll
+        for (int it = 0; it < TK / KY; ++it) {
+            const size_t kg = kb + ky + KY * it;
+            V4 v = {0u, 0u, 0u, 0u};
+            if (kg < a.k) {
+                if (pair_ok) {
+                    v = __builtin_nontemporal_load((const V4*)(x + kg * ld));
+                } else {
+#pragma unroll
+                    for (int e = 0; e < RPL; ++e) {
+                        const T t = (row + e < a.rows) ? x[kg * ld + e] : E::zero();
+                        __builtin_memcpy((char*)&v + e * sizeof(T), &t, sizeof(T));
+                    }
+                }
+            }
+            buf[it] = v;
+        }
+#pragma unroll
+        for (int it = 0; it < TK / KY; ++it) {
+            const int kk = ky + KY * it;
+#pragma unroll
+            for (int e = 0; e < RPL; ++e) __builtin_memcpy(&tile[RPL * rp + e][kk], (const char*)&buf[it] + e * sizeof(T), sizeof(T));
+        }
+    } else {
+        constexpr int KY = 256 / TR;
+        const int rx = threadIdx.x % TR, ky = threadIdx.x / TR;
+        const size_t row = r0 + rx;
+        const T* x = X + row;
+#pragma unroll 4
+        for (int it = 0; it < TK / KY; ++it) {
+            const int kk = ky + KY * it;
+            const size_t kg = kb + kk;
+            tile[rx][kk] = (row < a.rows && kg < a.k) ? x[kg * ld] : E::zero();
+        }
+    }
+    __syncthreads();
+    const int c = threadIdx.x % CH;
+#pragma unroll 1
+    for (int pass = 0; pass < TR / RPP; ++pass) {
+        const int rl = pass * RPP + threadIdx.x / CH;
+        const size_t row = r0 + rl;
+        if (row >= a.rows) continue;
+        int s;
+        if constexpr (MODE == MODE_BOUND) {
+            const UBm bits = rowam[rl];
+            U am;
+            __builtin_memcpy(&am, &bits, sizeof(U));
+            s = (a.backend == kINT8 ? 5 : 7) - ilogb0(am);
+            if (kt == 0 && c == 0) {
+                ((int16_t*)((char*)a.sft0 + OZ2_ZW))[row] = (int16_t)s;
+                if (a.sft0_keep) ((int16_t*)((char*)a.sft0_keep + OZ2_ZW))[row] = (int16_t)s;
+            }
+        } else {
+            s = OZ2_ROW_SHIFT(a, row, kt == 0 && c == 0);
+        }
+        T v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = tile[rl][c * 4 + e];
+        emit4<T, MODE>(a, row, kb + c * 4, v, s);
+    }
+}
+template <typename T> __global__ void __launch_bounds__(256) extract_sym_pair_kernel(const SymStageArgs a, const SymStageArgs b, const unsigned nA, const int kmA, const int kmB) {
+    if (a.zero_words) {
+        unsigned* zp = (unsigned*)((char*)a.zero_p + OZ2_ZW);
+        for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < a.zero_words; i += gridDim.x * 256u) zp[i] = 0u;
+    }
+    if (blockIdx.x < nA) {
+        if (kmA) stage_kmajor_body<T, MODE_BOUND>(a, blockIdx.x);
+        else stage_sym_body<T, MODE_BOUND>(a, blockIdx.x);
+    } else {
+        if (kmB) stage_kmajor_body<T, MODE_BOUND>(b, blockIdx.x - nA);
+        else stage_sym_body<T, MODE_BOUND>(b, blockIdx.x - nA);
+    }
+}
+template <typename T> __global__ void __launch_bounds__(256) quantise_sym_pair_kernel(const SymStageArgs a, const SymStageArgs b, const unsigned nA, const int kmA, const int kmB) {
+    if (blockIdx.x < nA) {
+        if (kmA) stage_kmajor_body<T, MODE_MOD>(a, blockIdx.x);
+        else stage_sym_body<T, MODE_MOD>(a, blockIdx.x);
+    } else {
+        if (kmB) stage_kmajor_body<T, MODE_MOD>(b, blockIdx.x - nA);
+        else stage_sym_body<T, MODE_MOD>(b, blockIdx.x - nA);
+    }
+}
+
+// Row maxima of a symmetric-form operand as partial arrays, amax_pair_kernel's scheme (workgroup = 64 rows x one k split; no atomics, nothing to zero).  The
+// split's columns on the mirrored side of ALL 64 rows are read along kk (16 lanes = 128 contiguous bytes of a row, four rows per lane); the others -- stored
+// for every row, or crossed by the diagonal -- with lanes along the rows through the address rule.
+struct AmaxSymOperand : AmaxOperand {
+    int sym, herm;
+};
+template <typename T> __device__ __forceinline__ void amax_sym_body(const AmaxSymOperand& o, const unsigned bid, size_t k, size_t bw) {
+    const T* X = (const T*)((const char*)o.X + blockIdx.z * o.bx);
+    using E = ET<T>;
+    using U = typename E::U;
+    using UB = typename std::conditional<sizeof(U) == 8, unsigned long long, unsigned>::type;
+    UB* amax = (UB*)((char*)o.amax + blockIdx.z * bw);
+    const unsigned by = bid / o.row_groups, bxr = bid - by * o.row_groups;
+    const size_t rows = o.rows, ld = o.ld;
+    __shared__ U sm[5][64];
+    const size_t R0 = (size_t)bxr * 64;
+    const size_t kper = (k + o.parts - 1) / o.parts;
+    const size_t kbeg = (size_t)by * kper, kend = (kbeg + kper < k) ? kbeg + kper : k;
+    size_t sb, se, mb, me;  // columns read along the rows [sb, se) / along kk [mb, me)
+    if (o.sym == kSymLower) sb = kbeg, se = kend < R0 + 64 ? kend : R0 + 64, mb = kbeg > R0 + 64 ? kbeg : R0 + 64, me = kend;
+    else mb = kbeg, me = kend < R0 ? kend : R0, sb = kbeg > R0 ? kbeg : R0, se = kend;
+    auto take = [](const T& v, U& am) {
+        const U ar = (U)fabs(E::re(v)), ai = (U)fabs(E::im(v));
+        am = ar > am ? ar : am;
+        am = ai > am ? ai : am;
+    };
+    {
+        const int rl = threadIdx.x & 63, ky = threadIdx.x >> 6;
+        const size_t row = R0 + rl;
+        U am = 0;
+        if (row < rows) {
+            size_t kk = sb + ky;
+            for (; kk + 12 < se; kk += 16) {  // four loads in flight per thread
+                T v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = sym_at<T>(X, ld, row, kk + 4 * u, o.sym, o.herm);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) take(v[u], am);
+            }
+            for (; kk < se; kk += 4) take(sym_at<T>(X, ld, row, kk, o.sym, o.herm), am);
+        }
+        sm[ky][rl] = am;
+    }
+    {
+        const int kl = threadIdx.x & 15, rq = threadIdx.x >> 4;
+        U am[4] = {0, 0, 0, 0};
+        for (size_t kk = mb + kl; kk < me; kk += 16) {
+            T v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t row = R0 + rq + 16 * j;
+                v[j] = row < rows ? X[row * ld + kk] : E::zero();  // (the conjugate has the same magnitudes)
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) take(v[j], am[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int off = 8; off > 0; off >>= 1) {
+                const U w = __shfl_xor(am[j], off);
+                am[j] = w > am[j] ? w : am[j];
+            }
+            if (kl == 0) sm[4][rq + 16 * j] = am[j];
+        }
+    }
+    __syncthreads();
+    const size_t row = R0 + threadIdx.x;
+    if (threadIdx.x < 64 && row < rows) {
+        U m = sm[0][threadIdx.x];
+#pragma unroll
+        for (int y = 1; y < 5; ++y) m = sm[y][threadIdx.x] > m ? sm[y][threadIdx.x] : m;
+        UB bits;
+        __builtin_memcpy(&bits, &m, sizeof(U));
+        amax[(size_t)by * o.pstride + row] = bits;
+    }
+}
+template <typename T> __global__ void __launch_bounds__(256) amax_sym_pair_kernel(const AmaxSymOperand a, const AmaxSymOperand b, const unsigned nA, size_t k, size_t bw) {
+    const bool isB = blockIdx.x >= nA;
+    const AmaxSymOperand& o = isB ? b : a;
+    const unsigned bid = isB ? blockIdx.x - nA : blockIdx.x;
+    if (o.sym != kSymNone) amax_sym_body<T>(o, bid, k, bw);
+    else amax_strided_body<T>(o, bid, k, bw);
+}
+
+// Fast-mode shift of a symmetric-form operand: fast_shift_strided_body's geometry and, exactly, its accumulation order -- lane ty of a row adds the squares of
+// columns ty, ty + 32, ... ascending, then the width-32 trees -- with every element fetched through the address rule (eight chain steps of loads ahead of
+// their round-up FMAs; the depth does not enter the order).
+template <typename T>
+__device__ __forceinline__ void fast_shift_sym_body(const T* X, size_t ld, size_t rows, size_t k, int16_t* sft, float log2P, const unsigned bid, const int sym, const int herm) {
+    using E = ET<T>;
+    using U = typename E::U;
+    constexpr int RPL = 16 / (int)sizeof(T), RPB = 8 * RPL;
+    __shared__ U samax[32][RPB + 1], ssum[32][RPB + 1];
+    const int tx = threadIdx.x & 7, ty = threadIdx.x >> 3;
+    const size_t row0 = (size_t)bid * RPB + (size_t)tx * RPL;
+    U amax[RPL], sum[RPL];
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) amax[j] = 0, sum[j] = 0;
+    auto take = [&](const T& v, int j) {
+        const U ar = (U)fabs(E::re(v));
+        amax[j] = ar > amax[j] ? ar : amax[j];
+        sum[j] = sqr_add_ru<U>(ar, sum[j]);
+        if constexpr (E::cplx) {
+            const U ai = (U)fabs(E::im(v));
+            amax[j] = ai > amax[j] ? ai : amax[j];
+            sum[j] = sqr_add_ru<U>(ai, sum[j]);
+        }
+    };
+    if (row0 < rows) {
+        size_t col = ty;
+        for (; col + 7 * 32 < k; col += 8 * 32) {
+            T v[8][RPL];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int j = 0; j < RPL; ++j) v[u][j] = row0 + j < rows ? sym_at<T>(X, ld, row0 + j, col + 32 * u, sym, herm) : E::zero();
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int j = 0; j < RPL; ++j) take(v[u][j], j);
+        }
+        for (; col < k; col += 32) {
+#pragma unroll
+            for (int j = 0; j < RPL; ++j)
+                if (row0 + j < rows) take(sym_at<T>(X, ld, row0 + j, col, sym, herm), j);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) {
+        samax[ty][tx * RPL + j] = amax[j];
+        ssum[ty][tx * RPL + j] = sum[j];
+    }
+    __syncthreads();
+    const int ll = threadIdx.x & 31;
+    for (int rr = threadIdx.x >> 5; rr < RPB; rr += 8) {
+        const U s = tree32_sum_ru(ssum[ll][rr]);
+        const U m = tree32_max(samax[ll][rr]);
+        const size_t row = (size_t)bid * RPB + rr;
+        if (row < rows && ll == 0) sft[row] = (int16_t)(-fast_sft(m, s, log2P));
+    }
+}
+struct ShiftSymOperand : ShiftOperand {
+    int sym, herm;
+};
+template <typename T> __global__ void __launch_bounds__(256) fast_shift_sym_pair_kernel(const ShiftSymOperand a, const ShiftSymOperand b, size_t k, float log2P, size_t bw) {
+    const bool isB = blockIdx.x >= a.blocks;
+    const ShiftSymOperand& o = isB ? b : a;
+    const unsigned bid = isB ? blockIdx.x - a.blocks : blockIdx.x;
+    const T* X = (const T*)((const char*)o.X + blockIdx.z * o.bx);
+    int16_t* sft = (int16_t*)((char*)o.sft + blockIdx.z * bw);
+    if (o.kmajor) fast_shift_kmajor_body<T>(X, o.ld, k, sft, log2P, bid);
+    else if (o.sym != kSymNone) fast_shift_sym_body<T>(X, o.ld, o.rows, k, sft, log2P, bid, o.sym, o.herm);
+    else fast_shift_strided_body<T>(X, o.ld, o.rows, k, sft, log2P, bid);
+}
+
+// a symmetric-form operand is square (rows == k), row-strided, on INT8 planes, in a single GEMM; its partner is any general operand
+static bool sym_operand_ok(int sym, bool herm, bool kmajor, size_t rows, size_t k, int dtype) {
+    if (sym == kSymNone) return !herm;
+    return (sym == kSymLower || sym == kSymUpper) && !kmajor && rows == k && (!herm || is_complex(dtype));
+}
+template <typename T> static hipError_t launch_amax_sym_pair_t(hipStream_t stream, size_t k, const ExtractOperand& A, const ExtractOperand& B) {
+    auto mk = [](const ExtractOperand& o) {
+        AmaxSymOperand q{};
+        if (o.rows && !o.kmajor) {
+            q.X = o.X, q.ld = o.ld, q.rows = o.rows, q.bx = o.xstride, q.amax = o.amax, q.pstride = o.pstride, q.parts = o.parts;
+            q.row_groups = (unsigned)((o.rows + 63) / 64), q.sym = o.sym, q.herm = o.herm ? 1 : 0;
+        }
+        return q;
+    };
+    const AmaxSymOperand a = mk(A), b = mk(B);
+    const size_t nA = (size_t)a.row_groups * a.parts, nB = (size_t)b.row_groups * b.parts;
+    if (nA + nB == 0) return hipSuccess;
+    if (nA + nB > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(amax_sym_pair_kernel<T>, dim3((unsigned)(nA + nB)), dim3(256), 0, stream, a, b, (unsigned)nA, k, (size_t)0);
+    return hipGetLastError();
+}
+static hipError_t launch_amax_sym_pair(hipStream_t stream, int dtype, size_t k, const ExtractOperand& A, const ExtractOperand& B) {
+    if (g_batch.batch != 1 || A.one_read || B.one_read || !sym_operand_ok(A.sym, A.herm, A.kmajor, A.rows, k, dtype) ||
+        !sym_operand_ok(B.sym, B.herm, B.kmajor, B.rows, k, dtype))
+        return hipErrorInvalidValue;
+    switch (dtype) {
+    case kF32: return launch_amax_sym_pair_t<float>(stream, k, A, B);
+    case kF64: return launch_amax_sym_pair_t<double>(stream, k, A, B);
+    case kC32: return launch_amax_sym_pair_t<float2>(stream, k, A, B);
+    case kC64: return launch_amax_sym_pair_t<double2>(stream, k, A, B);
+    }
+    return hipErrorInvalidValue;
+}
+static SymStageArgs sym_args(const StageArgs& s, int sym, bool herm) {
+    SymStageArgs a{};
+    static_cast<StageArgs&>(a) = s;
+    a.sym = sym, a.herm = herm ? 1 : 0;
+    return a;
+}
+template <typename T, int MODE> static hipError_t launch_stage_sym_pair_t(hipStream_t stream, bool kmA, SymStageArgs a, bool kmB, const SymStageArgs& b, void* zero_p, size_t zero_bytes) {
+    const size_t nA = stage_blocks<T, MODE>(kmA, a), nB = stage_blocks<T, MODE>(kmB, b);
+    if (nA + nB == 0 || nA + nB > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if constexpr (MODE == MODE_BOUND) {
+        if (zero_p && zero_bytes) a.zero_p = (unsigned*)zero_p, a.zero_words = (unsigned)(zero_bytes / 4);
+        hipLaunchKernelGGL(extract_sym_pair_kernel<T>, dim3((unsigned)(nA + nB)), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
+    } else {
+        hipLaunchKernelGGL(quantise_sym_pair_kernel<T>, dim3((unsigned)(nA + nB)), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
+    }
+    return hipGetLastError();
+}
+template <int MODE> static hipError_t launch_stage_sym_pair(hipStream_t stream, int dtype, bool kmA, const SymStageArgs& a, bool kmB, const SymStageArgs& b, void* zero_p,
+                                                            size_t zero_bytes) {
+    switch (dtype) {
+    case kF32: return launch_stage_sym_pair_t<float, MODE>(stream, kmA, a, kmB, b, zero_p, zero_bytes);
+    case kF64: return launch_stage_sym_pair_t<double, MODE>(stream, kmA, a, kmB, b, zero_p, zero_bytes);
+    case kC32: return launch_stage_sym_pair_t<float2, MODE>(stream, kmA, a, kmB, b, zero_p, zero_bytes);
+    case kC64: return launch_stage_sym_pair_t<double2, MODE>(stream, kmA, a, kmB, b, zero_p, zero_bytes);
+    }
+    return hipErrorInvalidValue;
+}
+static hipError_t launch_extract_sym_pair(hipStream_t stream, int dtype, int backend, size_t k, size_t kp, const ExtractOperand& A, const ExtractOperand& B,
+                                          void* zero_p, size_t zero_bytes) {
+    if (g_batch.batch != 1 || backend != kINT8 || A.one_read || B.one_read || !sym_operand_ok(A.sym, A.herm, A.kmajor, A.rows, k, dtype) ||
+        !sym_operand_ok(B.sym, B.herm, B.kmajor, B.rows, k, dtype))
+        return hipErrorInvalidValue;
+    const SymStageArgs a = sym_args(extract_args(backend, k, kp, A), A.sym, A.herm), b = sym_args(extract_args(backend, k, kp, B), B.sym, B.herm);
+    return launch_stage_sym_pair<MODE_BOUND>(stream, dtype, A.kmajor, a, B.kmajor, b, zero_p, zero_bytes);
+}
+static hipError_t launch_quantise_sym_pair(hipStream_t stream, int dtype, int backend, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& A,
+                                           const QuantOperand& B) {
+    if (g_batch.batch != 1 || backend != kINT8 || A.lo2 || B.lo2 || A.f6_rows || B.f6_rows || A.nf || B.nf ||
+        !sym_operand_ok(A.sym, A.herm, A.kmajor, A.rows, k, dtype) || !sym_operand_ok(B.sym, B.herm, B.kmajor, B.rows, k, dtype))
+        return hipErrorInvalidValue;
+    const SymStageArgs a = sym_args(quantise_args(backend, t_begin, t_end, k, kp, A), A.sym, A.herm),
+                       b = sym_args(quantise_args(backend, t_begin, t_end, k, kp, B), B.sym, B.herm);
+    return launch_stage_sym_pair<MODE_MOD>(stream, dtype, A.kmajor, a, B.kmajor, b, nullptr, 0);
+}
+static hipError_t launch_fast_shift_sym_pair(hipStream_t stream, int dtype, int backend, unsigned N, size_t k, const QuantOperand& A, const QuantOperand& B) {
+    if (g_batch.batch != 1 || backend != kINT8 || !sym_operand_ok(A.sym, A.herm, A.kmajor, A.rows, k, dtype) || !sym_operand_ok(B.sym, B.herm, B.kmajor, B.rows, k, dtype))
+        return hipErrorInvalidValue;
+    const float log2P = GEMMUL8_LOG2P_INT8[N - 2];
+    const size_t rpb = 8 * (16 / (is_f32(dtype) ? 4 : 8) / (is_complex(dtype) ? 2 : 1));  // rows per workgroup of the row-strided forms
+    auto operand = [&](const QuantOperand& o) {
+        const size_t blocks = o.kmajor ? o.rows : (o.rows + rpb - 1) / rpb;
+        ShiftSymOperand q{};
+        q.X = o.X, q.ld = o.ld, q.rows = o.rows, q.bx = o.xstride, q.sft = o.sft, q.blocks = (unsigned)blocks, q.kmajor = o.kmajor ? 1 : 0;
+        q.sym = o.sym, q.herm = o.herm ? 1 : 0;
+        return q;
+    };
+    if (A.rows + B.rows > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    const ShiftSymOperand a = operand(A), b = operand(B);
+    const dim3 grid(a.blocks + b.blocks);
+    switch (dtype) {
+    case kF32: hipLaunchKernelGGL(fast_shift_sym_pair_kernel<float>, grid, dim3(256), 0, stream, a, b, k, log2P, (size_t)0); break;
+    case kF64: hipLaunchKernelGGL(fast_shift_sym_pair_kernel<double>, grid, dim3(256), 0, stream, a, b, k, log2P, (size_t)0); break;
+    case kC32: hipLaunchKernelGGL(fast_shift_sym_pair_kernel<float2>, grid, dim3(256), 0, stream, a, b, k, log2P, (size_t)0); break;
+    case kC64: hipLaunchKernelGGL(fast_shift_sym_pair_kernel<double2>, grid, dim3(256), 0, stream, a, b, k, log2P, (size_t)0); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -210,6 +210,40 @@ GEMMUL8_API int gemmul8_syr2k(void *stream, int dtype, int backend, int uplo, in
                               size_t lda, const void *B, size_t ldb, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
                               void *work, double *timers_ns);
 
+/* Product with a symmetric matrix of which ONE triangle is stored: C = alpha*A*B + beta*C (side = LEFT, A is m x m) or C = alpha*B*A + beta*C
+ * (side = RIGHT, A is n x n); B and C are m x n, ka = the order of A.  All four types (the plain transpose for the complex types); side takes 0 / 1 or
+ * the hipblasSideMode_t values 141 / 142, uplo as in gemmul8_syrk.  alpha and beta are of the element type, host or device, detected as elsewhere.
+ * INT8 backend only (GEMMUL8_FP8: GEMMUL8_E_UNSUPPORTED -- the FP6 panel writer has no symmetric form).
+ *   - The materialised matrix: Afull is the ka x ka matrix BLAS defines from the triangle named by uplo, Afull(i,j) = Afull(j,i) = the stored entry.
+ *     gemmul8_hemm: the mirrored entry is the conjugate and the diagonal is the real part of the stored diagonal -- the stored imaginary part of a
+ *     diagonal entry counts as 0, whatever the memory holds.  No byte of the other strict triangle of A or of the lda padding is ever read: a NaN there,
+ *     or in HEMM's diagonal imaginary parts, reaches nothing.  Afull is never materialised: the scaling kernels read A through the triangle, in place.
+ *   - Bit identity: the whole m x n window of C holds, bit for bit, what gemmul8_gemm puts there in non-finite mode 0 on the INT8 backend with Afull
+ *     materialised --
+ *       LEFT:   gemmul8_gemm(dtype, GEMMUL8_INT8, N, N, m, n, m, alpha, Afull, ka, B, ldb, beta, C, ldc, ...);
+ *       RIGHT:  gemmul8_gemm(dtype, GEMMUL8_INT8, N, T, m, n, n, alpha, B, ldb, Afull, ka, beta, C, ldc, ...), gemmul8_hemm: the same with (N, C).
+ *     Afull^T = Afull (HEMM: Afull^H = Afull), so the RIGHT form is BLAS's B*A.  It is stated with T / C because in both cases the symmetric operand
+ *     then enters the scaling kernels in the ROW-STRIDED form: the fast mode's round-up sums depend on the lane an element lands in -- the only part of
+ *     the scaling whose bits depend on the operand's form -- so both sides have ONE summation order to reproduce, the strided form's (lane ty of a row
+ *     takes columns ty, ty + 32, ... ascending, then the width-32 tree).  In accurate mode the bits do not depend on the form (maxima, and per-element
+ *     bytes given the shift; tests/test_symm_premise.py pins this on the oracle).
+ *   - `work` holds gemmul8_work_size(is_complex, GEMMUL8_INT8, m, n, ka, num_moduli, 0, 0, NULL, NULL) bytes: the equivalent GEMM's workspace.
+ *   - beta == 0 never reads C; no byte of the ldc padding is written; A and B are never written; C must not overlap A or B.
+ *   - m == 0 or n == 0: GEMMUL8_OK, C untouched.  Bad side / uplo, a null pointer, ka > 2^17, dtype or backend out of range: GEMMUL8_E_ARG, answered
+ *     before any HIP call; num_moduli out of the type's range: GEMMUL8_E_NUM_MODULI.
+ *   - timers_ns, stream order and capture safety (timers_ns == NULL) as in gemmul8_gemm.
+ *   - gemmul8_set_nonfinite_mode is ignored: the call behaves as mode 0.
+ * No counterpart in the reference (it emulates GEMM only). */
+enum { GEMMUL8_LEFT = 0, GEMMUL8_RIGHT = 1 };
+GEMMUL8_API int gemmul8_symm(void *stream, int dtype, int backend, int side, int uplo, size_t m, size_t n, const void *alpha, const void *A,
+                             size_t lda, const void *B, size_t ldb, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
+                             void *work, double *timers_ns);
+/* The same with a Hermitian A (see "the materialised matrix" above): dtype GEMMUL8_C / GEMMUL8_Z only (S / D: GEMMUL8_E_ARG -- BLAS has no real HEMM);
+ * alpha and beta are COMPLEX scalars of the element type (unlike gemmul8_herk). */
+GEMMUL8_API int gemmul8_hemm(void *stream, int dtype, int backend, int side, int uplo, size_t m, size_t n, const void *alpha, const void *A,
+                             size_t lda, const void *B, size_t ldb, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
+                             void *work, double *timers_ns);
+
 /* D(i, j) += bias[i] for a column-major m x n real matrix: the broadcast bias of a hipblasLtMatmul BIAS epilogue, applied by the hook after
  * the emulated GEMM (one more rounding than the vendor's fused form).  S / D only.  No counterpart in the reference. */
 GEMMUL8_API int gemmul8_add_row_bias(void *stream, int dtype, size_t m, size_t n, void *D, size_t ldd, const void *bias);
