@@ -38,7 +38,7 @@ _lib = None
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
            "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
            "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk", "gemmul8_syr2k",
-           "gemmul8_symm", "gemmul8_hemm"]
+           "gemmul8_symm", "gemmul8_hemm", "gemmul8_her2k"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
 
@@ -129,6 +129,8 @@ def bind(L):
     L.gemmul8_syr2k.restype = C.c_int
     L.gemmul8_syr2k.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    L.gemmul8_her2k.restype = C.c_int
+    L.gemmul8_her2k.argtypes = L.gemmul8_syr2k.argtypes
     L.gemmul8_symm.restype = C.c_int
     L.gemmul8_symm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
@@ -308,6 +310,44 @@ def syr2k(A, B, num_moduli, uplo="L", trans="N", fastmode=False, alpha=1.0, beta
     rc = lib().gemmul8_syr2k(st, _dtype_code(dt), INT8, UPLO[uplo], OPS[trans], n, k, al.ctypes.data, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0),
                              be.ctypes.data, C_out.data_ptr(), C_out.stride(0), num_moduli, int(fastmode), work.data_ptr(), tm)
     check(rc, "gemmul8_syr2k")
+    return C_out, (list(tm) if timers else None), work
+
+
+def her2k_work_size(n, k, num_moduli):
+    """Bytes of workspace gemmul8_her2k needs: that of the equivalent complex GEMM (n, n, k)."""
+    return work_size(True, INT8, n, n, k, num_moduli)[0]
+
+
+def her2k(A, B, num_moduli, uplo="L", trans="N", fastmode=False, alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, timers=False):
+    """One triangle of C = alpha*A*B^H + conj(alpha)*B*A^H + beta*C (trans "N", A and B are n x k) or alpha*A^H*B + conj(alpha)*B^H*A + beta*C
+    (trans "C", A and B are k x n) through gemmul8_her2k: complex types, INT8 backend, a COMPLEX alpha and a REAL beta.  With
+    W = `gemm(A, B, opA=trans, opB="C" if trans == "N" else "N")` every stored entry is alpha*W[i,j] + conj(alpha*W[j,i]) + beta*C[i,j] in the fused form
+    include/gemmul8_c.h states; the diagonal's imaginary part is +0.0 (the incoming one is ignored); the other strict triangle of C_out is neither read
+    nor written.  A, B and C_out are column-major matrices held as tensors of shape (cols, rows), as in `gemm`; A and B may have different leading
+    dimensions (views: `lda` = tensor.stride(0)) or be the same tensor; a fresh C_out is zero-filled.  Returns (C, timers_ns or None, work)."""
+    import numpy as np
+    import torch
+    dt = A.dtype
+    if not dt.is_complex:
+        raise TypeError("her2k takes complex64 / complex128 (use syr2k for the real types)")
+    if trans not in ("N", "C"):
+        raise ValueError("trans is 'N' or 'C'")
+    for X in (A, B):
+        assert X.is_cuda and X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]
+    if B.dtype != dt or B.shape != A.shape or (C_out is not None and (C_out.dtype != dt or C_out.dim() != 2 or C_out.stride(1) != 1)):
+        raise TypeError("A, B and C_out must share one dtype, A and B one shape, and every column must be contiguous")
+    n, k = (A.shape[1], A.shape[0]) if trans == "N" else (A.shape[0], A.shape[1])
+    if C_out is None:
+        C_out = torch.zeros((n, n), dtype=dt, device=A.device)
+    if work is None:
+        work = torch.empty(her2k_work_size(n, k, num_moduli), dtype=torch.uint8, device=A.device)
+    al = np.array([alpha], dtype=np.complex64 if dt == torch.complex64 else np.complex128)
+    be = np.array([beta], dtype=np.float32 if dt == torch.complex64 else np.float64)
+    tm = (C.c_double * 4)() if timers else None
+    st = stream if stream is not None else torch.cuda.current_stream(A.device).cuda_stream
+    rc = lib().gemmul8_her2k(st, _dtype_code(dt), INT8, UPLO[uplo], OPS[trans], n, k, al.ctypes.data, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0),
+                             be.ctypes.data, C_out.data_ptr(), C_out.stride(0), num_moduli, int(fastmode), work.data_ptr(), tm)
+    check(rc, "gemmul8_her2k")
     return C_out, (list(tm) if timers else None), work
 
 

@@ -786,4 +786,198 @@ hipError_t launch_crt_tri(hipStream_t stream, int dtype, unsigned N, size_t n, i
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Hermitian rank-2k update (gemmul8_her2k).  C_mid holds the residues of the full square W = op(A) op(B)^H; a stored entry needs W_ij = (x, y) AND the
+// mirrored W_ji = (u, v):
+//   p = x + u, q = y - v, r = y + v, t = x - u
+//   Re = fma(beta, cx, fma(-ai, r, ar * p)),  Im = fma(beta, cy, fma(ai, t, ar * q))     (diagonal: cy counts as 0, Im = +0.0)
+// For a fixed column j the residues of W_ji lie ld_mid apart, so the kernel works on PAIRS of T x T tiles, one workgroup per pair (I, J) / (J, I) of the
+// stored triangle.  Phase 1 reads the mirror tile (J, I) in ITS natural layout (crt_load: 8 contiguous bytes of every plane per thread, 4 complex rows
+// of one column), reconstructs (u, v) to the element type exactly as crt_unit does and writes them to LDS; phase 2 reads the own tile (I, J) the same way,
+// fetches (u, v) transposed from LDS, combines, and stores down C's columns.  Reconstructed values, not residue bytes, cross the LDS: T * T elements,
+// whatever the moduli count.
+// T = 64: a column segment of a residue plane is 64 complex int8 = one whole 128-byte line (T = 32 reads half lines, each line by two workgroups), and
+// the LDS image of a complex128 tile is the 64 KiB a workgroup may declare -- two workgroups of 4 waves per CU, 2 waves per SIMD (512-thread workgroups
+// at 4 waves per SIMD spilled: the kernel needs 140 - 162 VGPRs); T = 128 does not fit the LDS.  Not measured against T = 32.
+// LDS image: mirror element (r, q) [r = mirror row = own column, q = mirror column = own row] lives in row r at chunk her2k_chunk(r, q) of T chunks of one
+// element each.  Padding the rows cannot free the transposed access of conflicts: a thread owns 4 consecutive q, so the 16 lanes of one column hit chunks
+// 4 g + e, four bank slots only.  The chunk is therefore rotated inside its group of 4 by (q >> 4) [complex64: (q >> 5) + 2 (r & 1)] and the row by
+// r >> 2: phase 2's read e of lanes g = 0..15 (ds_read_b128: every 16-lane group holds each g once; ds_read_b64: g x two rows r) then covers all
+// 16 (32) slots of the 256-byte bank row, and phase 1's write of 8 (16) contiguous lanes g to one q covers 8 (16) consecutive chunks.
+#define OZ2_HER2K_TILE 64
+#define OZ2_HER2K_BLOCK 256
+template <typename U> __device__ __forceinline__ unsigned her2k_chunk(unsigned r, unsigned q) {
+    constexpr unsigned SH = sizeof(U) == 8 ? 4u : 5u;
+    const unsigned rot = sizeof(U) == 8 ? 0u : 2u * (r & 1u);
+    return (((q & ~3u) | ((q + (q >> SH) + rot) & 3u)) + (r >> 2)) & (OZ2_HER2K_TILE - 1);
+}
+
+// the 4 complex values of one unit (rows row0 .. row0 + 3 of column col), scaled: crt_unit's accumulation order, crt_reduce and scalb, unchanged
+template <typename U, int NMAX>
+__device__ __forceinline__ void her2k_recon(const CrtArgs& a, const typename CrtVec<int8_t, 8, 2>::Vec (&c)[NMAX], size_t row0, size_t col, U (&out)[8]) {
+    double Sh[8], Sl[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) Sh[e] = 0.0, Sl[e] = 0.0;
+#pragma unroll
+    for (unsigned t = 0; t < (unsigned)NMAX; ++t) {
+        if (t < a.N) {
+            if (a.use_dd) {
+                const double qh = a.qh[t], ql = a.ql[t];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const double cd = (double)c[t].v[e];
+                    Sh[e] = fma(qh, cd, Sh[e]);
+                    Sl[e] = fma(ql, cd, Sl[e]);
+                }
+            } else {
+                const double q1 = a.q1[t];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) Sh[e] = fma(q1, (double)c[t].v[e], Sh[e]);
+            }
+        }
+    }
+    const int sB = (int)a.sftB[col];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const size_t row = row0 + r;
+        const int sft = (row < a.m ? (int)a.sftA[row] : 0) + sB;
+        out[2 * r] = scalb<U>((U)crt_reduce(a, Sh[2 * r], Sl[2 * r]), sft);
+        out[2 * r + 1] = scalb<U>((U)crt_reduce(a, Sh[2 * r + 1], Sl[2 * r + 1]), sft);
+    }
+}
+
+template <typename U, int NMAX>
+__global__ void __launch_bounds__(OZ2_HER2K_BLOCK) crt_her2k_kernel(const CrtArgs a) {
+    constexpr unsigned T = OZ2_HER2K_TILE, COLS = OZ2_HER2K_BLOCK / 16;  // a column of the tile takes 16 threads (4 rows each); COLS columns per pass
+    static_assert(T == 64 && T % COLS == 0, "16 threads x 4 rows per tile column");
+    typedef U U2 __attribute__((ext_vector_type(2)));
+    __shared__ __attribute__((aligned(16))) U2 mir[T * T];
+    using Vec = typename CrtVec<int8_t, 8, 2>::Vec;
+    const unsigned It = blockIdx.x, Jt = blockIdx.y;  // own tile: rows of block It, columns of block Jt
+    if (a.tri == 1 ? It < Jt : It > Jt) return;     // (the whole workgroup: nobody waits at the barrier)
+    const unsigned g = threadIdx.x & 15u, cl = threadIdx.x >> 4;
+    const size_t n = a.m;
+
+    // phase 1: the mirror tile (Jt, It) -- rows of block Jt (own columns), columns of block It (own rows)
+#pragma unroll 1
+    for (unsigned c0 = 0; c0 < T; c0 += COLS) {
+        const unsigned q = c0 + cl;
+        const size_t row0 = (size_t)Jt * T + 4 * g, col = (size_t)It * T + q;
+        if (row0 < n && col < n) {  // (rows in [n, mp) of a plane exist; columns >= n do not)
+            Vec cb[NMAX];
+            const CrtPos pos{col, row0, true};
+            crt_load<int8_t, 8, 2, NMAX>(a, pos, 0, cb);
+            U uv[8];
+            her2k_recon<U, NMAX>(a, cb, row0, col, uv);
+#pragma unroll
+            for (unsigned e = 0; e < 4; ++e) {
+                const unsigned r = 4 * g + e;
+                mir[r * T + her2k_chunk<U>(r, q)] = U2{uv[2 * e], uv[2 * e + 1]};
+            }
+        }
+    }
+    __syncthreads();
+
+    U ar = (U)a.alpha[0], ai = (U)a.alpha[1], be = (U)a.beta[0];
+    if (a.mode == 5) {  // device scalars: a complex alpha, a real beta
+        ar = ((const U*)a.alpha_dev)[0];
+        ai = ((const U*)a.alpha_dev)[1];
+        be = ((const U*)a.beta_dev)[0];
+    }
+    const bool reads_c = be != (U)0;
+
+    // phase 2: the own tile (It, Jt)
+#pragma unroll 1
+    for (unsigned c0 = 0; c0 < T; c0 += COLS) {
+        const unsigned jl = c0 + cl;
+        const size_t i0 = (size_t)It * T + 4 * g, col = (size_t)Jt * T + jl;
+        if (i0 >= n || col >= n) continue;
+        if (a.tri == 1 ? i0 + 3 < col : i0 > col) continue;  // wholly outside the triangle (a diagonal pair only)
+        Vec cb[NMAX];
+        const CrtPos pos{col, i0, true};
+        crt_load<int8_t, 8, 2, NMAX>(a, pos, 0, cb);
+        U xy[8];
+        her2k_recon<U, NMAX>(a, cb, i0, col, xy);
+        U* Cc = (U*)a.C + (col * a.ldc + i0) * 2;
+        auto stored = [&](size_t row) { return row < n && (a.tri == 1 ? row >= col : row <= col); };
+        const bool full = i0 + 4 <= n && (a.tri == 1 ? i0 >= col : i0 + 3 <= col);
+        U oldc[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) oldc[e] = (U)0;
+        if (reads_c) {
+            if (full) {
+                __builtin_memcpy(oldc, Cc, sizeof(oldc));
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (stored(i0 + e / 2)) oldc[e] = Cc[e];
+            }
+        }
+        U outv[8];
+#pragma unroll
+        for (unsigned e = 0; e < 4; ++e) {
+            const unsigned qi = 4 * g + e;
+            const U2 m = mir[jl * T + her2k_chunk<U>(jl, qi)];
+            const bool diag = i0 + e == col;
+            const U x = xy[2 * e], y = xy[2 * e + 1], u = m.x, v = m.y;
+            const U cx = oldc[2 * e], cy = diag ? (U)0 : oldc[2 * e + 1];
+            const U p = x + u, q = y - v, r = y + v, t = x - u;
+            outv[2 * e] = fmaU<U>(be, cx, fmaU<U>(-ai, r, ar * p));
+            outv[2 * e + 1] = diag ? (U)0 : fmaU<U>(be, cy, fmaU<U>(ai, t, ar * q));
+        }
+        if (full) {
+            typedef U VecU __attribute__((ext_vector_type(8)));
+            VecU ov;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ov[e] = outv[e];
+            if ((reinterpret_cast<uintptr_t>(Cc) & (sizeof(VecU) - 1)) == 0) __builtin_nontemporal_store(ov, (VecU*)Cc);
+            else __builtin_memcpy(Cc, outv, sizeof(outv));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (stored(i0 + e / 2)) Cc[e] = outv[e];
+        }
+    }
+}
+
+hipError_t launch_crt_her2k(hipStream_t stream, int dtype, unsigned N, size_t n, int tri, const void* Cmid, size_t ld_mid, size_t plane_stride,
+                            const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc) {
+    if (n == 0) return hipSuccess;
+    if ((tri != 1 && tri != 2) || !is_complex(dtype)) return hipErrorInvalidValue;
+    const size_t nt = (n + OZ2_HER2K_TILE - 1) / OZ2_HER2K_TILE;
+    if (nt > 65535) return hipErrorInvalidValue;  // gridDim.y
+    CrtArgs a{};
+    a.Cmid = Cmid;
+    a.ld_mid = ld_mid;
+    a.plane_stride = plane_stride;
+    a.m = n;
+    a.n = n;
+    a.sftA = sftA;
+    a.sftB = sftB;
+    a.C = C;
+    a.ldc = ldc;
+    a.tri = tri;
+    a.herm = 1;
+    fill_crt_tables(a, dtype, kINT8, N);
+    if (scalars_on_device) {
+        a.mode = 5;
+        a.alpha_dev = alpha;
+        a.beta_dev = beta;
+    } else {  // a complex alpha, a REAL beta
+        a.mode = 0;
+        if (is_f32(dtype)) a.alpha[0] = ((const float*)alpha)[0], a.alpha[1] = ((const float*)alpha)[1], a.beta[0] = *(const float*)beta;
+        else a.alpha[0] = ((const double*)alpha)[0], a.alpha[1] = ((const double*)alpha)[1], a.beta[0] = *(const double*)beta;
+    }
+    dim3 grid((unsigned)nt, (unsigned)nt);  // a tile pair outside the triangle leaves at once
+#define OZ2_CRT_HER2K(U)                                                                                             \
+    do {                                                                                                            \
+        if (N > 14) hipLaunchKernelGGL((crt_her2k_kernel<U, 20>), grid, dim3(OZ2_HER2K_BLOCK), 0, stream, a);       \
+        else hipLaunchKernelGGL((crt_her2k_kernel<U, 14>), grid, dim3(OZ2_HER2K_BLOCK), 0, stream, a);              \
+    } while (0)
+    if (dtype == kC32) OZ2_CRT_HER2K(float);
+    else OZ2_CRT_HER2K(double);
+#undef OZ2_CRT_HER2K
+    return hipGetLastError();
+}
+
 }  // namespace oz2

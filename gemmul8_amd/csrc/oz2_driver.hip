@@ -830,6 +830,55 @@ int gemmul8_syr2k(void* stream_, int dtype, int backend, int uplo, int trans, si
     return rank_k(kSyr2k, (hipStream_t)stream_, dtype, backend, uplo, trans, n, k, alpha, A, lda, B, ldb, beta, C, ldc, N, fastmode, work, timers_ns);
 }
 
+// ---- Hermitian rank-2k update (no counterpart in the reference).  alpha goes on op(A) op(B)^H and conj(alpha) on op(B) op(A)^H, so the call is not one GEMM
+// with one scalar (SYR2K's K-concatenation does not apply) -- but the second term is the conjugate transpose of the first: with W = op(A) op(B)^H, ONE
+// ordinary GEMM (trans, trans == N ? C : N) over the full square with inner dimension k, C_ij = alpha W_ij + conj(alpha W_ji) + beta C_ij.  Scaling and
+// residue GEMMs are gemmul8_gemm's (A and B keep their own shifts, every element is quantised once, k <= 2^17); the CRT reconstructs W_ij and W_ji for
+// every stored entry and applies alpha behind the reconstruction (launch_crt_her2k; tests/test_her2k_premise.py).
+int gemmul8_her2k(void* stream_, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void* alpha, const void* A, size_t lda, const void* B,
+                  size_t ldb, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (timers_ns) timers_ns[0] = timers_ns[1] = timers_ns[2] = timers_ns[3] = 0.0;
+    if (dtype < 0 || dtype > 3 || backend < 0 || backend > 1) return GEMMUL8_E_ARG;
+    if (!is_complex(dtype)) return GEMMUL8_E_ARG;  // BLAS has no real HER2K
+    if (uplo == 122) uplo = GEMMUL8_LOWER;  // hipblasFillMode_t
+    else if (uplo == 121) uplo = GEMMUL8_UPPER;
+    trans = norm_op(trans);
+    if ((uplo != GEMMUL8_LOWER && uplo != GEMMUL8_UPPER) || (trans != 0 && trans != 2)) return GEMMUL8_E_ARG;
+    if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
+    if (!alpha || !beta || !A || !B || !C || !work) return GEMMUL8_E_ARG;
+    if (k > (size_t(1) << 17)) return GEMMUL8_E_ARG;
+    if (backend == kFP8) return GEMMUL8_E_UNSUPPORTED;  // the pair CRT reads int8 residues
+    if (n == 0 || k == 0) return GEMMUL8_OK;
+    gemmul8_layout L;
+    int rc = gemmul8_get_layout(dtype, backend, n, n, k, N, work, nullptr, nullptr, 0, 0, &L);
+    if (rc) return rc;
+    Timer* T = timers_ns ? thread_timer() : nullptr;
+    if (T && hipEventRecord(T->ev[0], stream) != hipSuccess) {
+        (void)hipGetLastError();
+        T = nullptr;
+    }
+    rc = scale_nf(stream, dtype, backend, trans, trans == 0 ? 2 : 0, n, n, k, A, lda, B, ldb, N, fastmode, 0, N, &L, 0, 0, false);
+    if (rc) return rc;
+    if (T) OZ2_HIP(hipEventRecord(T->ev[1], stream));
+    rc = gemmul8_lowprec_gemm(stream, dtype, backend, n, n, k, N, 0, N, &L);
+    if (rc) return rc;
+    if (T) OZ2_HIP(hipEventRecord(T->ev[2], stream));
+    OZ2_HIP(launch_crt_her2k(stream, dtype, N, n, uplo == GEMMUL8_LOWER ? 1 : 2, L.C_mid, L.mp, L.sizeC, L.sftA, L.sftB, alpha, beta, scalars_on_device(alpha), C, ldc));
+    if (T) {
+        OZ2_HIP(hipEventRecord(T->ev[3], stream));
+        OZ2_HIP(hipEventSynchronize(T->ev[3]));
+        float ms;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[0], T->ev[1]));
+        timers_ns[0] = ms * 1e6;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[1], T->ev[2]));
+        timers_ns[1] = ms * 1e6;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[2], T->ev[3]));
+        timers_ns[3] = ms * 1e6;
+    }
+    return GEMMUL8_OK;
+}
+
 // ---- product with a symmetric / Hermitian matrix of which one triangle is stored (no counterpart in the reference).  Afull is never materialised: the
 // call is the equivalent GEMM -- LEFT: (N, N) Afull B, RIGHT: (N, T) / (N, C) B op(Afull) -- whose symmetric operand the scaling kernels read through the
 // triangle (the symmetric form of oz2_scale.hip; row-strided on either side, so the fast mode's round-up sums have one order).  Everything behind the

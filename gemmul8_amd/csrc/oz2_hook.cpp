@@ -12,6 +12,8 @@
 //   hipblas{S,D,C,Z}syrk(_64), hipblas{C,Z}herk(_64)                        yes: one triangle through gemmul8_syrk / gemmul8_herk (INT8 backend, k <= 2^17; HERK: real
 //                                                                             alpha / beta, N / C only); everything else is the native routine's, see try_syrk_impl
 //   hipblas{S,D,C,Z}syr2k(_64)                                              yes: one triangle through gemmul8_syr2k (INT8 backend, k <= 2^16, N / T only); see try_syrk_impl
+//   hipblas{C,Z}her2k(_64)                                                  yes: one triangle through gemmul8_her2k (INT8 backend, k <= 2^17, N / C only; complex alpha,
+//                                                                             real beta); see try_syrk_impl
 //   hipblas{S,D,C,Z}symm(_64), hipblas{C,Z}hemm(_64)                        yes: the product with a symmetric / Hermitian matrix through gemmul8_symm / gemmul8_hemm (INT8 backend,
 //                                                                             order of A <= 2^17; one triangle of A read in place); see try_symm_impl
 //   hipblasLtMatmul, hipblasLtDestroy                                       yes (PyTorch's float32 matmuls): the plain case only, see lt_try
@@ -31,7 +33,7 @@
 //                                  once        workspace pre-sizing, applied when a SKIP_SCALE switch is on (hook.cu:232-281,656-662)
 //  the rest is this build's only:
 //   GEMMUL8_FP8_BOUND, GEMMUL8_NONFINITE
-//                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace); under `ieee` SYRK / HERK / SYR2K
+//                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace); under `ieee` SYRK / HERK / SYR2K / HER2K
 //                                              calls are not emulated (try_syrk_impl), nor are SYMM / HEMM calls (try_symm_impl)
 //   GEMMUL8_MIN_FLOPS              per call    unset or 0 = emulate every selected call (the reference's behaviour); `auto` = a fitted cost model decides
 //                                              per call (below_floor); a number = floor on 2*m*n*k.  The first call a floor declines is logged once.
@@ -41,7 +43,7 @@
 //   GEMMUL8_HOOK_ROCBLAS           per call    "1" = the rocBLAS entry points above act
 //   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
 //   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call);
-//                                              a line each for hipblas{S,D,C,Z}syrk, hipblas{C,Z}herk, hipblas{S,D,C,Z}syr2k, hipblas{S,D,C,Z}symm and
+//                                              a line each for hipblas{S,D,C,Z}syrk, hipblas{C,Z}herk, hipblas{S,D,C,Z}syr2k, hipblas{C,Z}her2k, hipblas{S,D,C,Z}symm and
 //                                              hipblas{C,Z}hemm when one was seen
 //   GEMMUL8_HOOK_VERBOSE           per call    "1" = say why a hipblasLtMatmul call was left to the native routine
 //
@@ -69,13 +71,13 @@
 
 // The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
 // `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
-// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_symm / gemmul8_hemm: every such call then goes to the native routine); the shim, which binds to this
+// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_her2k / gemmul8_symm / gemmul8_hemm: every such call then goes to the native routine); the shim, which binds to this
 // project's own libgemmul8.so, requires every entry.
 #define OZ2_ABI(X)                                                                                          \
     X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
     X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
     X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak))) X(herk, __attribute__((weak))) \
-    X(syr2k, __attribute__((weak))) X(symm, __attribute__((weak))) X(hemm, __attribute__((weak)))
+    X(syr2k, __attribute__((weak))) X(symm, __attribute__((weak))) X(hemm, __attribute__((weak))) X(her2k, __attribute__((weak)))
 #ifndef OZ2_HOOK_SHIM
 #define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
 OZ2_ABI(X)
@@ -558,13 +560,14 @@ struct NativeScope {
     NativeScope(const NativeScope&) = delete;
     NativeScope& operator=(const NativeScope&) = delete;
 };
-enum { kSYRK = 0, kHERK = 1, kSYR2K = 2 };  // the rank-k routines of try_syrk
-const char* const kRankName[3] = {"SYRK", "HERK", "SYR2K"};
+enum { kSYRK = 0, kHERK = 1, kSYR2K = 2, kHER2K = 3, kRankKinds = 4 };  // the rank-k routines of try_syrk
+const char* const kRankName[kRankKinds] = {"SYRK", "HERK", "SYR2K", "HER2K"};
 struct HookStats {
     std::atomic<unsigned long long> emu_calls{0}, nat_calls{0};
     std::atomic<unsigned long long> emu_mflops{0}, nat_mflops{0};  // 2 m n k batch / 1e6 (x 4 for complex), rounded down
-    // hipblas?syrk [0] / hipblas?herk [1] / hipblas?syr2k [2]: n (n + 1) k / 1e6 (x 4; syr2k: x 2)
-    std::atomic<unsigned long long> emu_syrk[3] = {{0}, {0}, {0}}, nat_syrk[3] = {{0}, {0}, {0}}, emu_syrk_mflops[3] = {{0}, {0}, {0}}, nat_syrk_mflops[3] = {{0}, {0}, {0}};
+    // hipblas?syrk [0] / hipblas?herk [1] / hipblas?syr2k [2] / hipblas?her2k [3]: n (n + 1) k / 1e6 (x 4 for complex; syr2k, her2k: x 2)
+    std::atomic<unsigned long long> emu_syrk[kRankKinds] = {{0}, {0}, {0}, {0}}, nat_syrk[kRankKinds] = {{0}, {0}, {0}, {0}}, emu_syrk_mflops[kRankKinds] = {{0}, {0}, {0}, {0}},
+                                    nat_syrk_mflops[kRankKinds] = {{0}, {0}, {0}, {0}};
     // hipblas?symm [0] / hipblas?hemm [1]: 2 m n ka / 1e6 (x 4 for complex)
     std::atomic<unsigned long long> emu_symm[2] = {{0}, {0}}, nat_symm[2] = {{0}, {0}}, emu_symm_mflops[2] = {{0}, {0}}, nat_symm_mflops[2] = {{0}, {0}};
     static void dump();
@@ -579,7 +582,7 @@ void HookStats::dump() {
     HookStats& h = hook_stats();
     std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu GEMM calls (%.3f TFLOP), native %llu GEMM calls through the hooked entry points (%.3f TFLOP)\n",
                  h.emu_calls.load(), h.emu_mflops.load() * 1e-6, h.nat_calls.load(), h.nat_mflops.load() * 1e-6);
-    for (int kind = 0; kind < 3; ++kind)
+    for (int kind = 0; kind < kRankKinds; ++kind)
         if (h.emu_syrk[kind].load() + h.nat_syrk[kind].load())
             std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu %s calls (%.3f TFLOP), native %llu %s calls through the hooked entry points (%.3f TFLOP)\n",
                          h.emu_syrk[kind].load(), kRankName[kind], h.emu_syrk_mflops[kind].load() * 1e-6, h.nat_syrk[kind].load(), kRankName[kind],
@@ -623,7 +626,8 @@ bool floor_model_declines(int dtype, double m, double n, double k, unsigned N, b
 // quiet = a query (gemmul8_hook_would_emulate), not a call: no log line.  syrk = 1: a SYRK call, 2: a HERK call (m == n): a number is a floor on
 // n (n + 1) k, `auto` takes the GEMM model's decision for (n, n, k) -- native and emulated SYRK / HERK are both about half their GEMMs; no scan of
 // either has been fitted.  syrk = 3: a SYR2K call: a number is a floor on 2 n (n + 1) k; the caller passes 2 k, so that `auto` takes the GEMM model's
-// decision for (n, n, 2 k) -- no SYR2K scan has been fitted either.
+// decision for (n, n, 2 k) -- no SYR2K scan has been fitted either.  syrk = 4: a HER2K call: a number is a floor on 8 n (n + 1) k (the routine's real
+// operations), `auto` takes the GEMM model's decision for (n, n, k), the one GEMM the call runs -- no HER2K scan has been fitted.
 bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch = 1.0, bool quiet = false, int syrk = 0) {
     const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
     if (!s || !*s) return false;  // the reference's behaviour: every selected call is emulated
@@ -633,14 +637,15 @@ bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast,
         declined = floor_model_declines(dtype, m, n, k, N, fast, backend, batch);
     } else {
         const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
-        declined = f && (syrk ? n * (n + 1.0) * k : 2.0 * m * n * k) < (double)f;  // (SYR2K: k is 2 k here)
+        declined = f && (syrk == 4 ? 8.0 * n * (n + 1.0) * k : syrk ? n * (n + 1.0) * k : 2.0 * m * n * k) < (double)f;  // (SYR2K: k is 2 k here)
     }
     if (declined && !quiet) {
-        static std::once_flag told[4];  // GEMM, SYRK, HERK, SYR2K
+        static std::once_flag told[1 + kRankKinds];  // GEMM, SYRK, HERK, SYR2K, HER2K
         std::call_once(told[syrk], [&] {
             if (syrk)
                 std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %c%s n = %.0f, k = %.0f (%u moduli) stays on the native routine -- calls below the "
-                                     "floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], kRankName[syrk - 1], n, syrk == 3 ? 0.5 * k : k, N);
+                                     "floor are NOT emulated%s (this message is printed once)\n", s, "SDCZ"[dtype], kRankName[syrk - 1], n, syrk == 3 ? 0.5 * k : k, N,
+                             syrk == 4 ? "; no HER2K scan has been fitted: a number is a floor on 8 n (n + 1) k, `auto` is the GEMM model's decision for (n, n, k)" : "");
             else
                 std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cGEMM %.0f x %.0f x %.0f (batch %.0f, %u moduli%s) stays on the native routine -- "
                                      "calls below the floor are NOT emulated (this message is printed once)\n",
@@ -748,10 +753,12 @@ bool try_emulate(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* sta
 // hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: below_floor's SYRK / HERK form.  GEMMUL8_DIST and the skip-scaling switches do not apply.
 // hipblas{S,D,C,Z}syr2k (kind = kSYR2K; B != nullptr): one triangle of alpha (A B^T + B A^T) + beta C through gemmul8_syr2k -- the same selection, with
 // k <= 2^16 (the equivalent GEMM's inner dimension is 2 pad256(k)), that GEMM's workspace, and below_floor's SYR2K form.
+// hipblas{C,Z}her2k (kind = kHER2K; B != nullptr; complex alpha, real beta): one triangle of alpha A B^H + conj(alpha) B A^H + beta C through gemmul8_her2k --
+// the same selection with N / C, k <= 2^17, the workspace of the GEMM (n, n, k), and below_floor's HER2K form.
 bool try_syrk_impl(int kind, hipblasHandle_t handle, int dtype, int uplo, int trans, int n, int k, const void* alpha, const void* A, int lda, const void* B,
                    int ldb, const void* beta, void* C, int ldc, hipblasStatus_t* status) {
-    const bool herm = kind == kHERK, two = kind == kSYR2K;
-    if (!(two ? (bool)abi().syr2k : herm ? (bool)abi().herk : (bool)abi().syrk)) return false;
+    const bool her2 = kind == kHER2K, herm = kind == kHERK || her2, two = kind == kSYR2K;
+    if (!(her2 ? (bool)abi().her2k : two ? (bool)abi().syr2k : herm ? (bool)abi().herk : (bool)abi().syrk)) return false;
     const char* const name = kRankName[kind];
     const int max_k = two ? kMaxK / 2 : kMaxK;
     if ((uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) || (trans != HIPBLAS_OP_N && trans != (herm ? HIPBLAS_OP_C : HIPBLAS_OP_T)))
@@ -759,7 +766,7 @@ bool try_syrk_impl(int kind, hipblasHandle_t handle, int dtype, int uplo, int tr
     Selection s;
     if (!selection_from_env(dtype, &s)) {
         if (s.N != 0) {
-            static std::once_flag told[3];
+            static std::once_flag told[kRankKinds];
             std::call_once(told[kind], [&] {
                 std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %c%s calls use the native routine\n", kTypes[dtype].nmod, s.N,
                              kTypes[dtype].max_moduli, "SDCZ"[dtype], name);
@@ -768,15 +775,15 @@ bool try_syrk_impl(int kind, hipblasHandle_t handle, int dtype, int uplo, int tr
         return false;
     }
     if (s.backend == GEMMUL8_FP8 || k > max_k) {
-        static std::once_flag told[3][2];  // the backend, the k range: one notice each
+        static std::once_flag told[kRankKinds][2];  // the backend, the k range: one notice each
         std::call_once(told[kind][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
             std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for k <= %d only (GEMMUL8_BACKEND=%d, k=%d): using the native routine "
                                  "for such calls\n", name, max_k, s.backend, k);
         });
         return false;
     }
-    if (nonfinite_ieee()) {  // gemmul8_syrk / herk / syr2k ignore the non-finite mode: a NaN or Inf operand would come back as finite numbers
-        static std::once_flag told[3];
+    if (nonfinite_ieee()) {  // gemmul8_syrk / herk / syr2k / her2k ignore the non-finite mode: a NaN or Inf operand would come back as finite numbers
+        static std::once_flag told[kRankKinds];
         std::call_once(told[kind], [&] {
             std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: %s has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
                                  "for such calls\n", name);
@@ -788,14 +795,14 @@ bool try_syrk_impl(int kind, hipblasHandle_t handle, int dtype, int uplo, int tr
     if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
     const size_t kw = two ? 2 * (((size_t)k + 255) / 256 * 256) : (size_t)k;  // the inner dimension of the GEMM whose workspace the call needs
     const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)n, (size_t)n, kw, s.N, 0, 0, nullptr, nullptr);
-    static const char* const what[3] = {"workC (syrk)", "workC (herk)", "workC (syr2k)"};
+    static const char* const what[kRankKinds] = {"workC (syrk)", "workC (herk)", "workC (syr2k)", "workC (her2k)"};
     if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, what[kind]); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
-    const int rc = two ? abi().syr2k(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, B, (size_t)ldb, beta, C, (size_t)ldc,
+    const int rc = (two || her2) ? (her2 ? abi().her2k : abi().syr2k)(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, B, (size_t)ldb, beta, C, (size_t)ldc,
                                      s.N, s.fast, l.sp->wC.ptr, nullptr)
                        : (herm ? abi().herk : abi().syrk)(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, beta, C,
                                                           (size_t)ldc, s.N, s.fast, l.sp->wC.ptr, nullptr);
     if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
-        static std::once_flag warned[3];
+        static std::once_flag warned[kRankKinds];
         std::call_once(warned[kind], [&] {
             std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a %s call (status %d; type %d, n=%d k=%d): using the native routine for such calls\n", name,
                          rc, dtype, n, k);
@@ -811,12 +818,12 @@ bool try_syrk(int kind, hipblasHandle_t handle, int dtype, int uplo, int trans, 
     if (tl_native_depth > 0) return false;
     const int64_t lim = 2147483647;
     if (n <= 0 || k <= 0 || !alpha || !beta || !A || !C || n > lim || k > lim || lda > lim || ldc > lim) return false;
-    if (kind == kSYR2K && (!B || ldb > lim)) return false;
+    if ((kind == kSYR2K || kind == kHER2K) && (!B || ldb > lim)) return false;
     const bool served = try_syrk_impl(kind, handle, dtype, uplo, trans, (int)n, (int)k, alpha, A, (int)lda, B, (int)ldb, beta, C, (int)ldc, status);
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
     if (on) {
         HookStats& h = hook_stats();
-        const unsigned long long mf = (unsigned long long)((double)n * ((double)n + 1.0) * (double)k * (dtype >= 2 ? 4.0 : 1.0) * (kind == kSYR2K ? 2.0 : 1.0) * 1e-6);
+        const unsigned long long mf = (unsigned long long)((double)n * ((double)n + 1.0) * (double)k * (dtype >= 2 ? 4.0 : 1.0) * (kind == kSYR2K || kind == kHER2K ? 2.0 : 1.0) * 1e-6);
         (served ? h.emu_syrk : h.nat_syrk)[kind].fetch_add(1, std::memory_order_relaxed);
         (served ? h.emu_syrk_mflops : h.nat_syrk_mflops)[kind].fetch_add(mf, std::memory_order_relaxed);
     }
@@ -1373,6 +1380,14 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
         if (try_symm(KIND, handle, CODE, (int)side, (int)uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;              \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc);                \
     }
+// hipblas{C,Z}her2k: a complex alpha, R = the real type of beta
+#define OZ2_HER2K_HOOK(NAME, T, R, I, CODE)                                                                                             \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
+                         I lda, const T* B, I ldb, const R* beta, T* C, I ldc) {                                                        \
+        hipblasStatus_t st;                                                                                                             \
+        if (try_syrk(kHER2K, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;          \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc);              \
+    }
 // hipblas{C,Z}herk: R = the real type of alpha and beta
 #define OZ2_HERK_HOOK(NAME, T, R, I, CODE)                                                                                              \
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const R* alpha, const T* A, \
@@ -1407,6 +1422,10 @@ OZ2_HERK_HOOK(hipblasCherk, hipComplex, float, int, GEMMUL8_C)
 OZ2_HERK_HOOK(hipblasCherk_64, hipComplex, float, int64_t, GEMMUL8_C)
 OZ2_HERK_HOOK(hipblasZherk, hipDoubleComplex, double, int, GEMMUL8_Z)
 OZ2_HERK_HOOK(hipblasZherk_64, hipDoubleComplex, double, int64_t, GEMMUL8_Z)
+OZ2_HER2K_HOOK(hipblasCher2k, hipComplex, float, int, GEMMUL8_C)
+OZ2_HER2K_HOOK(hipblasCher2k_64, hipComplex, float, int64_t, GEMMUL8_C)
+OZ2_HER2K_HOOK(hipblasZher2k, hipDoubleComplex, double, int, GEMMUL8_Z)
+OZ2_HER2K_HOOK(hipblasZher2k_64, hipDoubleComplex, double, int64_t, GEMMUL8_Z)
 OZ2_SYMM_HOOK(hipblasChemm, kHEMM, hipComplex, int, GEMMUL8_C)
 OZ2_SYMM_HOOK(hipblasChemm_64, kHEMM, hipComplex, int64_t, GEMMUL8_C)
 OZ2_SYMM_HOOK(hipblasZhemm, kHEMM, hipDoubleComplex, int, GEMMUL8_Z)
@@ -1420,6 +1439,7 @@ OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
 #undef OZ2_ROCBLAS_HOOK
 #undef OZ2_GEMM_EX_HOOK
 #undef OZ2_HERK_HOOK
+#undef OZ2_HER2K_HOOK
 #undef OZ2_SYMM_HOOK
 #undef OZ2_SYR2K_HOOK
 #undef OZ2_SYRK_HOOK

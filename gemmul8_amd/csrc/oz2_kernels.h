@@ -181,6 +181,12 @@ hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, si
 hipError_t launch_crt_tri(hipStream_t stream, int dtype, unsigned N, size_t n, int tri, const void* Cmid, size_t ld_mid, size_t plane_stride,
                           const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc,
                           bool herm = false);
+// gemmul8_her2k (complex types, INT8 residues): C_mid holds the FULL square W = op(A) op(B)^H; every stored entry (i, j) of the triangle `tri` becomes
+// alpha W_ij + conj(alpha W_ji) + beta C_ij from the reconstructed W_ij (shifts sftA[i] + sftB[j]) and W_ji (sftA[j] + sftB[i]) -- the formula and the
+// tile-pair kernel are above crt_her2k_kernel.  alpha points to a COMPLEX scalar, beta to a REAL one (device: two values and one).  Diagonal: the incoming
+// imaginary part counts as 0, +0.0 is stored.  The other strict triangle of C is neither read nor written; beta == 0 never reads C.
+hipError_t launch_crt_her2k(hipStream_t stream, int dtype, unsigned N, size_t n, int tri, const void* Cmid, size_t ld_mid, size_t plane_stride,
+                            const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc);
 
 hipError_t launch_row_bias(hipStream_t stream, int dtype, size_t m, size_t n, void* D, size_t ldd, const void* bias);
 hipError_t launch_add_f64(hipStream_t stream, double* dst, const double* src, size_t count);  // dst += src (16-byte aligned arrays)

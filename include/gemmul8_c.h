@@ -187,7 +187,7 @@ GEMMUL8_API int gemmul8_herk(void *stream, int dtype, int backend, int uplo, int
 
 /* Symmetric rank-2k update of one triangle: C = alpha*(A*B^T + B*A^T) + beta*C (trans = N, A and B are n x k) or
  * C = alpha*(A^T*B + B^T*A) + beta*C (trans = T, A and B are k x n); the plain transpose for the complex types too (HER2K, which applies alpha to one term
- * and conj(alpha) to the other, is not one GEMM with one scalar and is not provided).  All four types; uplo and trans as in gemmul8_syrk (N / T only,
+ * and conj(alpha) to the other, is not one GEMM with one scalar: it is gemmul8_her2k below, by another route).  All four types; uplo and trans as in gemmul8_syrk (N / T only,
  * the 0 / 1 and the hipBLAS values).  INT8 backend only (GEMMUL8_FP8: GEMMUL8_E_UNSUPPORTED, for gemmul8_syrk's reason).
  *   - The identity: A B^T + B A^T = P Q^T with P = [A, Z, B, Z] and Q = [B, Z, A, Z], Z = the n x (kh - k) zero block, kh = k rounded up to a multiple
  *     of 256 -- P and Q are n x 2 kh, and the second half of each starts on a 256 boundary (trans = T: everything transposed, P^T Q).
@@ -207,6 +207,32 @@ GEMMUL8_API int gemmul8_herk(void *stream, int dtype, int backend, int uplo, int
  *   - gemmul8_set_nonfinite_mode is ignored: the call behaves as mode 0.
  * No counterpart in the reference (it emulates GEMM only). */
 GEMMUL8_API int gemmul8_syr2k(void *stream, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void *alpha, const void *A,
+                              size_t lda, const void *B, size_t ldb, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
+                              void *work, double *timers_ns);
+
+/* Hermitian rank-2k update of one triangle: C = alpha*A*B^H + conj(alpha)*B*A^H + beta*C (trans = N, A and B are n x k) or
+ * C = alpha*A^H*B + conj(alpha)*B^H*A + beta*C (trans = C, A and B are k x n).  dtype GEMMUL8_C / GEMMUL8_Z only (S / D: GEMMUL8_E_ARG); trans takes
+ * 0 / 2 or the hipblasOperation_t values 111 / 113 (T, 1 / 112: GEMMUL8_E_ARG); uplo as in gemmul8_syrk.  alpha points to a COMPLEX scalar of the element
+ * type, beta to a REAL one (float / double); both on the host or both on the device, detected as elsewhere.  INT8 backend only (GEMMUL8_FP8:
+ * GEMMUL8_E_UNSUPPORTED -- the pair CRT is built for int8 residues).
+ *   - The route: the second term is the conjugate transpose of the first.  With W = op(A) op(B)^H -- ONE ordinary GEMM over the full square, inner
+ *     dimension k -- C_ij = alpha W_ij + conj(alpha W_ji) + beta C_ij.  A and B are scaled as that GEMM scales them (each keeps its own row shifts, every
+ *     element is quantised once, k <= 2^17), and alpha is applied behind the CRT, where it costs no bits.
+ *   - These are the bits.  Let W be what gemmul8_gemm(dtype, GEMMUL8_INT8, trans, trans == N ? C : N, n, n, k, 1, A, lda, B, ldb, 0, W, n, ...) writes in
+ *     non-finite mode 0, W_ij = (x, y), W_ji = (u, v), the old C_ij = (cx, cy) [cy counts as 0 on the diagonal whatever the memory holds; (cx, cy) count as
+ *     0 and are not read when beta == 0], alpha = (ar, ai).  In the element type, one rounding each:
+ *         p = x + u,  q = y - v,  r = y + v,  t = x - u
+ *         Re = fma(beta, cx, fma(-ai, r, ar * p))
+ *         Im = fma(beta, cy, fma( ai, t, ar * q))        (diagonal: Im = +0.0)
+ *   - No byte of the other strict triangle of C or of the ldc padding is read or written; beta == 0 never reads C.
+ *   - A == B (the same pointer) is allowed.
+ *   - `work` holds gemmul8_work_size(1, GEMMUL8_INT8, n, n, k, num_moduli, 0, 0, NULL, NULL) bytes: the equivalent GEMM's workspace.
+ *   - timers_ns, stream order and capture safety (timers_ns == NULL) as in gemmul8_syrk.
+ *   - n == 0 or k == 0: GEMMUL8_OK, C untouched.  Bad uplo / trans / dtype / backend, a null pointer, k > 2^17: GEMMUL8_E_ARG, answered before any HIP
+ *     call; num_moduli out of the type's range: GEMMUL8_E_NUM_MODULI.
+ *   - gemmul8_set_nonfinite_mode is ignored: the call behaves as mode 0.
+ * No counterpart in the reference (it emulates GEMM only). */
+GEMMUL8_API int gemmul8_her2k(void *stream, int dtype, int backend, int uplo, int trans, size_t n, size_t k, const void *alpha, const void *A,
                               size_t lda, const void *B, size_t ldb, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
                               void *work, double *timers_ns);
 

@@ -6,7 +6,9 @@ commit's), loaded in the same process; a second GEMM column of this build shows 
 --herk: gemmul8_herk against gemmul8_gemm(A, A^H) instead -- ZHERK n = k = 8192 at 20 moduli and CHERK at 13 (--shapes / --moduli / --types override).
 --syr2k: gemmul8_syr2k against what replaced it before the routine existed -- gemmul8_gemm on the materialised P = [A, Z, B, Z] and Q = [B, Z, A, Z]
 (the GEMM alone, and with the two packing copies in front of it) -- and against the native hipblas?syr2k: D, 14 moduli, n = 8192 with k = 4096 and k = 512.
-usage: python tools/syrk_ab.py [--herk | --syr2k] [--gemm-lib parent/libgemmul8.so] [--rounds 9] [--shapes 8192x8192,8192x1024,16384x512] [--moduli 14] [--out FILE]"""
+--her2k: gemmul8_her2k against what a caller does today -- gemmul8_gemm for W = A B^H, then torch operations for alpha W + (alpha W)^H over the full
+square -- and against the native hipblasZher2k: Z, 14 moduli, n = 8192 with k = 4096, 512 and 64 (profiles/her2k_ab.json).
+usage: python tools/syrk_ab.py [--herk | --syr2k | --her2k] [--gemm-lib parent/libgemmul8.so] [--rounds 9] [--shapes 8192x8192,8192x1024,16384x512] [--moduli 14] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +28,7 @@ ap.add_argument("--gemm-lib", default=None)
 ap.add_argument("--rounds", type=int, default=9)
 ap.add_argument("--herk", action="store_true")
 ap.add_argument("--syr2k", action="store_true")
+ap.add_argument("--her2k", action="store_true")
 ap.add_argument("--shapes", default=None)
 ap.add_argument("--moduli", type=int, default=None, help="default: 14 (SYRK); --herk: 20 for Z, 13 for C")
 ap.add_argument("--types", default=None, help="SYRK: D; --herk: Z,C")
@@ -44,8 +47,8 @@ TYPES = {"S": (g.S, torch.float32, np.float32, np.float32), "D": (g.D, torch.flo
          "C": (g.Cx, torch.complex64, np.complex64, np.float32)}   # code, tensor type, GEMM scalar type, rank-k scalar type
 
 
-def native_syr2k(ty):
-    """hipblas{S,D}syr2k on the current stream through the hipBLAS this process has mapped (PyTorch's copy), else the system's"""
+def native_syr2k(ty, routine="syr2k"):
+    """hipblas{S,D}syr2k (or hipblas{C,Z}her2k: the same argument list) on the current stream through the hipBLAS this process has mapped (PyTorch's copy), else the system's"""
     path = "libhipblas.so"
     with open("/proc/self/maps") as f:
         for line in f:
@@ -55,7 +58,7 @@ def native_syr2k(ty):
     hb = C.CDLL(path)
     handle = C.c_void_p()
     assert hb.hipblasCreate(C.byref(handle)) == 0 and hb.hipblasSetStream(handle, C.c_void_p(st)) == 0
-    fn = getattr(hb, f"hipblas{ty}syr2k")
+    fn = getattr(hb, f"hipblas{ty}{routine}")
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     return lambda n, k, al, A, B, be, Cm: fn(handle, 122, 111, n, k, al.ctypes.data, A.data_ptr(), n, B.data_ptr(), n, be.ctypes.data, Cm.data_ptr(), n)
@@ -122,9 +125,67 @@ def syr2k_ab():
     return rows
 
 
+def her2k_ab():
+    rows = []
+    for ty, shape in ((t, s) for t in (a.types or "Z").split(",") for s in (a.shapes or "8192x4096,8192x512,8192x64").split(",")):
+        code, tdt, gdt, rdt = TYPES[ty]
+        N = a.moduli or 14
+        alpha = 0.75 - 0.25j
+        al, be, rbe = np.array([alpha], dtype=gdt), np.array([0.0], dtype=gdt), np.array([0.0], dtype=rdt)
+        one = np.array([1.0], dtype=gdt)
+        n, k = (int(x) for x in shape.split("x"))
+        A, B = (torch.randn((k, n), dtype=tdt, device="cuda") for _ in range(2))   # column-major n x k
+        W, Cout = (torch.zeros((n, n), dtype=tdt, device="cuda") for _ in range(2))
+        work = torch.empty(g.her2k_work_size(n, k, N), dtype=torch.uint8, device="cuda")
+        native = native_syr2k(ty, "her2k")
+        for fast in (0, 1):
+            def gemm_w(tm=None):
+                return this.gemmul8_gemm(st, code, g.INT8, 0, 2, n, n, k, one.ctypes.data, A.data_ptr(), n, B.data_ptr(), n, be.ctypes.data, W.data_ptr(), n, N, fast,
+                                         work.data_ptr(), None, None, 0, 0, 0, 0, tm)
+
+            def gemm_combine(tm=None):
+                rc = gemm_w(tm)
+                aw = W * alpha
+                torch.add(aw, aw.mH, out=Cout)   # W is held transposed, and so is Cout: the conjugate transpose is the same view on both
+                return rc
+
+            def her2k(tm=None):
+                return this.gemmul8_her2k(st, code, g.INT8, 0, 0, n, k, al.ctypes.data, A.data_ptr(), n, B.data_ptr(), n, rbe.ctypes.data, Cout.data_ptr(), n, N, fast,
+                                          work.data_ptr(), tm)
+            legs = [("her2k", her2k), ("gemm_w", gemm_w), ("gemm_combine", gemm_combine)]
+            if not fast:
+                legs.append(("native", lambda tm=None: native(n, k, al, A, B, rbe, Cout)))
+            ts = {name: [] for name, _ in legs}
+            for r in range(a.rounds + 2):
+                for name, fn in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    rc = fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    assert rc == 0, (name, rc)
+                    if r >= 2:
+                        ts[name].append(e0.elapsed_time(e1))
+            rec = {"type": ty, "n": n, "k": k, "moduli": N, "mode": "fast" if fast else "accurate", "rounds": a.rounds}
+            for name, fn in legs:
+                t = sorted(ts[name])
+                rec[name + "_ms"] = round(t[len(t) // 2], 4)
+                rec[name + "_min_ms"] = round(t[0], 4)
+                if name in ("her2k", "gemm_w"):
+                    tm = (C.c_double * 4)()
+                    assert fn(tm) == 0
+                    rec[name + "_phases_ms"] = {"scale": round(tm[0] * 1e-6, 4), "lowprec_gemm": round(tm[1] * 1e-6, 4), "crt": round(tm[3] * 1e-6, 4)}
+            rec["her2k_over_gemm_combine"] = round(rec["her2k_ms"] / rec["gemm_combine_ms"], 4)
+            if "native_ms" in rec:
+                rec["her2k_over_native"] = round(rec["her2k_ms"] / rec["native_ms"], 4)
+            rows.append(rec)
+            print(json.dumps(rec), flush=True)
+    return rows
+
+
 shapes = a.shapes or ("8192x8192" if a.herk else "8192x8192,8192x1024,16384x512")
-rows = syr2k_ab() if a.syr2k else []
-for ty, shape in ((t, s) for t in (() if a.syr2k else (a.types or ("Z,C" if a.herk else "D")).split(",")) for s in shapes.split(",")):
+rows = syr2k_ab() if a.syr2k else her2k_ab() if a.her2k else []
+for ty, shape in ((t, s) for t in (() if a.syr2k or a.her2k else (a.types or ("Z,C" if a.herk else "D")).split(",")) for s in shapes.split(",")):
     code, tdt, gdt, rdt = TYPES[ty]
     N = a.moduli or ((20 if ty == "Z" else 13) if a.herk else 14)
     al, be = np.array([1.0], dtype=gdt), np.array([0.0], dtype=gdt)      # the GEMM's scalars (complex for Z / C)
