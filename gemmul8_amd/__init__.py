@@ -17,6 +17,7 @@ INT8, FP8 = 0, 1
 OPS = {"N": 0, "T": 1, "C": 2}
 UPLO = {"L": 0, "U": 1}
 SIDE = {"L": 0, "R": 1}
+DIAG = {"N": 0, "U": 1}
 
 
 class Layout(C.Structure):
@@ -38,7 +39,7 @@ _lib = None
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
            "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
            "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk", "gemmul8_syr2k",
-           "gemmul8_symm", "gemmul8_hemm", "gemmul8_her2k"]
+           "gemmul8_symm", "gemmul8_hemm", "gemmul8_her2k", "gemmul8_trmm"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
 
@@ -136,6 +137,9 @@ def bind(L):
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
     L.gemmul8_hemm.restype = C.c_int
     L.gemmul8_hemm.argtypes = L.gemmul8_symm.argtypes
+    L.gemmul8_trmm.restype = C.c_int
+    L.gemmul8_trmm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
     L.gemmul8_set_fp8_bound_mode.restype = C.c_int
     L.gemmul8_set_fp8_bound_mode.argtypes = [C.c_int]
     L.gemmul8_set_nonfinite_mode.restype = C.c_int
@@ -398,6 +402,51 @@ def hemm(A, B, num_moduli, side="L", uplo="L", fastmode=False, alpha=1.0, beta=0
     if not A.dtype.is_complex:
         raise TypeError("hemm takes complex64 / complex128 (use symm for the real types)")
     return _symm("gemmul8_hemm", A, B, num_moduli, side, uplo, fastmode, alpha, beta, C_out, work, stream, timers)
+
+
+def trmm_work_size(is_complex, m, n, side, num_moduli):
+    """Bytes of workspace gemmul8_trmm needs: that of the equivalent GEMM, whose inner dimension is the order of A (m for side "L", n for "R")."""
+    return work_size(is_complex, INT8, m, n, m if SIDE[side] == 0 else n, num_moduli)[0]
+
+
+def trmm(A, B, num_moduli, side="L", uplo="L", trans="N", diag="N", alpha=1, fastmode=False, C_out=None, work=None, stream=None, timers=False):
+    """C = alpha*op(A)*B (side "L", A is m x m) or alpha*B*op(A) (side "R", A is n x n) with a TRIANGULAR A through gemmul8_trmm: only the triangle `uplo`
+    ("L" / "U") of A is read -- under diag "U" not even its diagonal, which counts as ones -- and the other half is zero; trans "N" / "T" / "C".  INT8
+    backend; bit-identical to `gemm(M, B)` (side "L") / `gemm(B, Mt, opB="T")` (side "R") with M = op(Atri) / its plain transpose Mt materialised, which
+    this call never does, at about half of that GEMM's matrix work.  There is no beta: C is never read.  C_out=None allocates; C_out=B is the in-place form
+    of classic BLAS.  alpha: a number, or a one-element device tensor of A's dtype.  A, B and C_out are column-major matrices held as tensors of shape
+    (cols, rows), as in `gemm`; views with a larger leading dimension are taken through tensor.stride(0).  Returns (C, timers_ns or None, work)."""
+    import numpy as np
+    import torch
+    dt = A.dtype
+    for X in (A, B):
+        assert X.is_cuda and X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]
+    if B.dtype != dt or A.shape[0] != A.shape[1] or (C_out is not None and (C_out.dtype != dt or C_out.dim() != 2 or C_out.stride(1) != 1)):
+        raise TypeError("A, B and C_out must share one dtype, A must be square, and every column must be contiguous")
+    n, m = B.shape
+    ka = m if SIDE[side] == 0 else n
+    if A.shape[0] != ka:
+        raise ValueError(f"A is of order {A.shape[0]}, side {side!r} of an {m} x {n} B needs {ka}")
+    if C_out is None:
+        C_out = torch.empty((n, m), dtype=dt, device=A.device)
+    elif tuple(C_out.shape) != (n, m):
+        raise ValueError(f"C_out is {tuple(C_out.shape)}, the product is {(n, m)}")
+    if work is None:
+        work = torch.empty(trmm_work_size(dt.is_complex, m, n, side, num_moduli), dtype=torch.uint8, device=A.device)
+    if isinstance(alpha, torch.Tensor):
+        if not alpha.is_cuda or alpha.dtype != dt or alpha.numel() != 1:
+            raise TypeError("a tensor alpha is one element of A's dtype on the device")
+        al_ptr = alpha.data_ptr()
+    else:
+        np_dt = {torch.float32: np.float32, torch.float64: np.float64, torch.complex64: np.complex64, torch.complex128: np.complex128}[dt]
+        al = np.array([alpha], dtype=np_dt)
+        al_ptr = al.ctypes.data
+    tm = (C.c_double * 4)() if timers else None
+    st = stream if stream is not None else torch.cuda.current_stream(A.device).cuda_stream
+    rc = lib().gemmul8_trmm(st, _dtype_code(dt), INT8, SIDE[side], UPLO[uplo], OPS[trans], DIAG[diag], m, n, al_ptr, A.data_ptr(), A.stride(0),
+                            B.data_ptr(), B.stride(0), C_out.data_ptr(), C_out.stride(0), num_moduli, int(fastmode), work.data_ptr(), tm)
+    check(rc, "gemmul8_trmm")
+    return C_out, (list(tm) if timers else None), work
 
 
 def gemm_batched(A, B, num_moduli, fastmode=False, opA="N", opB="N", alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, backend=INT8):

@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "../../include/gemmul8_c.h"
+#include "oz2_gemm_common.hpp"
 #include "oz2_kernels.h"
 #include "oz2_knobs.hpp"
 
@@ -256,8 +257,9 @@ static int bound_gemm_i8(hipStream_t stream, bool cplx, const gemmul8_layout* L,
 // gemmul8_symm / gemmul8_hemm: which operand of the equivalent GEMM is in symmetric form (oz2_kernels.h SymForm), passed down from symm() only
 struct SymSide {
     bool onB;   // false: the A side (side = LEFT), true: the B side (RIGHT)
-    int form;   // kSymLower / kSymUpper
+    int form;   // kSymLower / kSymUpper; gemmul8_trmm: with the kTri* bits of the triangular form
     bool herm;
+    bool conj = false;  // gemmul8_trmm, transA = C: the operand is conjugated where its planes are written (the operand's own `conj` flag)
 };
 // nf: non-finite mode 1 (gemmul8_set_nonfinite_mode) -- passed down from the whole-call entry points only; the phase-level entry points run mode 0
 // rows from which a row-strided operand takes the one-read extract (16 / 32 rows per workgroup): measured, DESIGN.md 3.4
@@ -312,6 +314,7 @@ static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int 
         if (srB) eb.amax = (char*)amax + (srA ? (size_t)ea.parts * srA * ub : 0), eb.parts = amax_parts_for(n, k, room * srB / (srA + srB) / srB);
     }
     if (sym) (sym->onB ? eb : ea).sym = sym->form, (sym->onB ? eb : ea).herm = sym->herm;
+    if (sym && sym->conj) (sym->onB ? eb : ea).conj = cplx;
     if (srA + srB) OZ2_HIP(launch_amax_pair(stream, dtype, k, ea, eb));
     const size_t zero_bytes = 4 * (L->mp + np);
     if (knobs().scale_fold) {
@@ -383,6 +386,7 @@ static int scale_finish_nf(void* stream_, int dtype, int backend, int op_A, int 
     oa.nf = ob.nf = nf;
     if (twinA) oa.lo2 = twinA->lo, oa.plane_stride2 = twinA->plane_stride, oa.part_stride2 = twinA->part_stride;
     if (sym) (sym->onB ? ob : oa).sym = sym->form, (sym->onB ? ob : oa).herm = sym->herm;
+    if (sym && sym->conj) (sym->onB ? ob : oa).conj = cplx;
     if (fastmode) {
         OZ2_HIP(launch_fast_shift_pair(stream, dtype, backend, N, k, oa, ob));
         if (nf) {  // flagged rows / columns: sentinel shifts before the quantise reads them
@@ -433,10 +437,12 @@ int gemmul8_scale(void* stream_, int dtype, int backend, int op_A, int op_B, siz
     return scale_nf(stream_, dtype, backend, op_A, op_B, m, n, k, A, lda, B, ldb, N, fastmode, t_begin, t_end, L, skipA, skipB, false);
 }
 
-int gemmul8_lowprec_gemm(void* stream_, int dtype, int backend, size_t m, size_t n, size_t k, unsigned N, unsigned t_begin,
-                         unsigned t_end, const gemmul8_layout* L) {
+// krange (KRange, oz2_gemm_common.hpp; passed down from trmm() only): the INT8 residue launches run only the K-steps of every tile's range
+static int lowprec_gemm_kr(void* stream_, int dtype, int backend, size_t m, size_t n, size_t k, unsigned N, unsigned t_begin, unsigned t_end,
+                           const gemmul8_layout* L, int krange) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!L) return GEMMUL8_E_ARG;
+    if (krange != 0 && backend != kINT8) return GEMMUL8_E_UNSUPPORTED;
     // the layout carries the padded inner dimension the planes were built with: a k that does not pad to it is a caller error (the FP8
     // K-concatenation below is exact only while 2 k 16^2 <= 2^24, so a placeholder k must not pass)
     if (padding256(k) != L->kp) return GEMMUL8_E_ARG;
@@ -555,7 +561,7 @@ int gemmul8_lowprec_gemm(void* stream_, int dtype, int backend, size_t m, size_t
     }
     if (!is_complex(dtype)) {
         OZ2_HIP(launch_gemm_i8_mod(stream, A_lo + (size_t)t_begin * L->sizeA, B_lo + (size_t)t_begin * L->sizeB, L->sizeA, L->sizeB, L->kp, m, n,
-                                   (int)t_begin, (int)t_end, (int8_t*)L->C_mid + (size_t)t_begin * L->sizeC, L->mp, L->sizeC, true));
+                                   (int)t_begin, (int)t_end, (int8_t*)L->C_mid + (size_t)t_begin * L->sizeC, L->mp, L->sizeC, true, 0, krange));
         return GEMMUL8_OK;
     }
     // complex (gemmul8_complex.hpp:154-206, conv_hi2mid_complex.hpp:9-127): per modulus X = ArBr, Y = AiBi,
@@ -570,14 +576,19 @@ int gemmul8_lowprec_gemm(void* stream_, int dtype, int backend, size_t m, size_t
         const unsigned t1 = std::min<unsigned>(t_end, t0 + (unsigned)chunk);
         int8_t* ry = rx + (size_t)(t1 - t0) * L->sizeC;
         OZ2_HIP(launch_gemm_i8_mod(stream, A_lo + (size_t)t0 * L->sizeA, B_lo + (size_t)t0 * L->sizeB, L->sizeA, L->sizeB, L->kp, m, n,
-                                   (int)t0, (int)t1, rx, L->mp, L->sizeC, false));  // X, Y: re-read by the Z launch right away
+                                   (int)t0, (int)t1, rx, L->mp, L->sizeC, false, 0, krange));  // X, Y: re-read by the Z launch right away
         OZ2_HIP(launch_gemm_i8_mod(stream, A_lo + L->part_strideA + (size_t)t0 * L->sizeA, B_lo + L->part_strideB + (size_t)t0 * L->sizeB,
-                                   L->sizeA, L->sizeB, L->kp, m, n, (int)t0, (int)t1, ry, L->mp, L->sizeC, false));
+                                   L->sizeA, L->sizeB, L->kp, m, n, (int)t0, (int)t1, ry, L->mp, L->sizeC, false, 0, krange));
         OZ2_HIP(launch_gemm_i8_cplx(stream, A_lo + 2 * L->part_strideA + (size_t)t0 * L->sizeA,
                                     B_lo + 2 * L->part_strideB + (size_t)t0 * L->sizeB, L->sizeA, L->sizeB, L->kp, m, n, (int)t0, (int)t1, rx,
-                                    ry, L->sizeC, (int8_t*)L->C_mid + (size_t)t0 * 2 * L->sizeC, L->mp, 2 * L->sizeC));
+                                    ry, L->sizeC, (int8_t*)L->C_mid + (size_t)t0 * 2 * L->sizeC, L->mp, 2 * L->sizeC, 0, krange));
     }
     return GEMMUL8_OK;
+}
+
+int gemmul8_lowprec_gemm(void* stream_, int dtype, int backend, size_t m, size_t n, size_t k, unsigned N, unsigned t_begin,
+                         unsigned t_end, const gemmul8_layout* L) {
+    return lowprec_gemm_kr(stream_, dtype, backend, m, n, k, N, t_begin, t_end, L, 0);
 }
 
 int gemmul8_crt(void* stream_, int dtype, int backend, unsigned N, size_t m, size_t n, const void* C_mid, size_t ld_mid,
@@ -941,6 +952,86 @@ int gemmul8_symm(void* stream_, int dtype, int backend, int side, int uplo, size
 int gemmul8_hemm(void* stream_, int dtype, int backend, int side, int uplo, size_t m, size_t n, const void* alpha, const void* A, size_t lda, const void* B,
                  size_t ldb, const void* beta, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
     return symm(kHemm, (hipStream_t)stream_, dtype, backend, side, uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc, N, fastmode, work, timers_ns);
+}
+
+// ---- product with a triangular matrix (no counterpart in the reference).  Atri -- the stored triangle, exact zeros in the other strict triangle, ones on
+// the diagonal under UNIT -- and M = op(Atri) are never materialised: the call is the equivalent GEMM -- LEFT: (N, N) M B, RIGHT: (N, T) B Mt, Mt the plain
+// transpose of M -- whose triangular operand the scaling kernels read through the stored triangle (the triangular form of oz2_scale.hip: row-strided on
+// either side and for every transA, so the fast mode's round-up sums have one lane order).  The residue GEMMs run, per tile, only the K-steps in which M can
+// be non-zero (KRange, oz2_gemm_common.hpp); the bound GEMM of the accurate mode stays the full rectangle.  CRT with beta = 0: C is never read, so C may be
+// B (B is read by the scaling phase only, C written by the CRT only, in stream order).
+static int trmm(hipStream_t stream, int dtype, int backend, int side, int uplo, int transA, int diag, size_t m, size_t n, const void* alpha, const void* A,
+                size_t lda, const void* B, size_t ldb, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    if (timers_ns) timers_ns[0] = timers_ns[1] = timers_ns[2] = timers_ns[3] = 0.0;
+    if (dtype < 0 || dtype > 3 || backend < 0 || backend > 1) return GEMMUL8_E_ARG;
+    if (side == 141) side = GEMMUL8_LEFT;  // hipblasSideMode_t
+    else if (side == 142) side = GEMMUL8_RIGHT;
+    if (uplo == 122) uplo = GEMMUL8_LOWER;  // hipblasFillMode_t
+    else if (uplo == 121) uplo = GEMMUL8_UPPER;
+    if (diag == 131) diag = GEMMUL8_NON_UNIT;  // hipblasDiagType_t
+    else if (diag == 132) diag = GEMMUL8_UNIT;
+    transA = norm_op(transA);
+    if ((side != GEMMUL8_LEFT && side != GEMMUL8_RIGHT) || (uplo != GEMMUL8_LOWER && uplo != GEMMUL8_UPPER) || transA < 0 || transA > 2 ||
+        (diag != GEMMUL8_NON_UNIT && diag != GEMMUL8_UNIT))
+        return GEMMUL8_E_ARG;
+    if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
+    if (!alpha || !A || !B || !C || !work) return GEMMUL8_E_ARG;
+    const size_t ka = side == GEMMUL8_LEFT ? m : n;
+    if (ka > (size_t(1) << 17)) return GEMMUL8_E_ARG;
+    if (backend == kFP8) return GEMMUL8_E_UNSUPPORTED;  // the FP6 panel writer has no triangular form
+    if (m == 0 || n == 0) return GEMMUL8_OK;
+    gemmul8_layout L;
+    int rc = gemmul8_get_layout(dtype, backend, m, n, ka, N, work, nullptr, nullptr, 0, 0, &L);
+    if (rc) return rc;
+    Timer* T = timers_ns ? thread_timer() : nullptr;
+    if (T && hipEventRecord(T->ev[0], stream) != hipSuccess) {
+        (void)hipGetLastError();
+        T = nullptr;
+    }
+    const bool left = side == GEMMUL8_LEFT, lowerA = uplo == GEMMUL8_LOWER;
+    // the operand's logical element (r, kk): LEFT M(r, kk), RIGHT Mt(r, kk) = M(kk, r).  It is Atri(r, kk) -- the stored half at the stored address -- for
+    // (LEFT, N) and (RIGHT, T / C), and Atri(kk, r) -- the mirrored half at the transposed address -- for (LEFT, T / C) and (RIGHT, N)
+    const bool stored = left == (transA == 0);
+    const int form = (lowerA ? kSymLower : kSymUpper) | (stored ? kTriStored : kTriMirrored) | (diag == GEMMUL8_UNIT ? kTriUnit : 0);
+    const SymSide sym{!left, form, false, transA == 2};
+    if (left) rc = scale_nf(stream, dtype, backend, 0, 0, m, n, ka, A, lda, B, ldb, N, fastmode, 0, N, &L, 0, 0, false, nullptr, &sym);
+    else rc = scale_nf(stream, dtype, backend, 0, 1, m, n, ka, B, ldb, A, lda, N, fastmode, 0, N, &L, 0, 0, false, nullptr, &sym);
+    if (rc) return rc;
+    if (T) OZ2_HIP(hipEventRecord(T->ev[1], stream));
+    // M is lower triangular when the stored triangle is the lower one and op = N, or the upper one and op = T / C
+    const bool lowerM = lowerA == (transA == 0);
+    const int krange = left ? (lowerM ? kKrALower : kKrAUpper) : (lowerM ? kKrBHigh : kKrBLow);
+    rc = lowprec_gemm_kr(stream, dtype, backend, m, n, ka, N, 0, N, &L, krange);
+    if (rc) return rc;
+    if (T) OZ2_HIP(hipEventRecord(T->ev[2], stream));
+    // beta = 0 lives where alpha lives: on the host, or -- the CRT reads both scalars through device pointers then -- in the first 16 bytes of the scratch
+    // region, which nothing uses any more once the residue GEMMs have run (zeroed by a kernel, in stream order: capture-safe)
+    const double zero[2] = {0.0, 0.0};  // the zero of every element type
+    const void* beta = zero;
+    if (scalars_on_device(alpha)) {
+        if (L.scratch_bytes < 16) return GEMMUL8_E_ARG;
+        OZ2_HIP(launch_zero(stream, L.scratch, 16));
+        beta = L.scratch;
+    }
+    rc = gemmul8_crt(stream, dtype, backend, N, m, n, L.C_mid, L.mp, L.sizeC, L.sftA, L.sftB, alpha, beta, C, ldc);
+    if (rc) return rc;
+    if (T) {
+        OZ2_HIP(hipEventRecord(T->ev[3], stream));
+        OZ2_HIP(hipEventSynchronize(T->ev[3]));
+        float ms;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[0], T->ev[1]));
+        timers_ns[0] = ms * 1e6;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[1], T->ev[2]));
+        timers_ns[1] = ms * 1e6;
+        OZ2_HIP(hipEventElapsedTime(&ms, T->ev[2], T->ev[3]));
+        timers_ns[3] = ms * 1e6;
+    }
+    return GEMMUL8_OK;
+}
+
+int gemmul8_trmm(void* stream_, int dtype, int backend, int side, int uplo, int transA, int diag, size_t m, size_t n, const void* alpha, const void* A,
+                 size_t lda, const void* B, size_t ldb, void* C, size_t ldc, unsigned N, int fastmode, void* work, double* timers_ns) {
+    return trmm((hipStream_t)stream_, dtype, backend, side, uplo, transA, diag, m, n, alpha, A, lda, B, ldb, C, ldc, N, fastmode, work, timers_ns);
 }
 
 int gemmul8_add_f64(void* stream_, double* dst, const double* src, size_t count) {

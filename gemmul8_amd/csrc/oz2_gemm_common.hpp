@@ -164,14 +164,34 @@ __device__ __forceinline__ void map_tile_tri(unsigned rem, const TileMapArgs& a,
     }
     map_trapezoid(rem - a.s_pairs, (unsigned)a.th, a.t0, a.m_th, tm, tn);
 }
+// K range of a tile (gemmul8_trmm: one operand of the product is M = op(Atri), triangular): the K-steps (BK = 128 bytes) in which the tile's 256 rows of the
+// A operand (krange 1, 2: the range follows tm) or 256 rows of the B operand (3, 4: tn) can hold a non-zero.  Every other K-step of the tile multiplies
+// residues of zeros, which add exactly 0 to an int32 accumulator: it is not run.  Ranges are never empty (kp is a multiple of 256: at least two K-steps).
+//   kKrALower  M(r, kk) = 0 for kk > r   [0, min(KT, 2 (tm + 1)))        kKrAUpper  M(r, kk) = 0 for kk < r   [2 tm, KT)
+//   kKrBLow    M(kk, j) = 0 for kk > j   [0, min(KT, 2 (tn + 1)))        kKrBHigh   M(kk, j) = 0 for kk < j   [2 tn, KT)
+// tests/test_trmm_krange.py holds a host mirror of this rule against brute force.
+enum KRange { kKrNone = 0, kKrALower = 1, kKrAUpper = 2, kKrBHigh = 3, kKrBLow = 4 };
+__host__ __device__ __forceinline__ void tile_krange(int krange, int KT, int tm, int tn, int& k0, int& k1) {
+    const int t = (krange == kKrALower || krange == kKrAUpper) ? tm : tn;
+    k0 = 0, k1 = KT;
+    if (krange == kKrALower || krange == kKrBLow) k1 = 2 * (t + 1) < KT ? 2 * (t + 1) : KT;
+    else if (krange != kKrNone) k0 = 2 * t;
+}
 // TRI: the instantiation may be launched with the triangular walk (the bound GEMM and the laboratory kernels never are: their code does not change)
-template <bool TRI = false>
+// KR (krange != 0; the K-ranged kernels of oz2_gemm_i8.hip only): tiles differ in length by up to KT : 2 and a workgroup takes the virtual tiles vb, vb + G, ...
+// statically, so the walk itself levels the work: every ODD full chunk of 256 is walked BACKWARDS.  A workgroup's position p in even chunks is 255 - p in odd
+// ones; with the tile-row index fastest (8 per group) and chunks that are whole row groups, whole planes or whole numbers of planes, position 255 - p is the
+// tile-row (and tile-column) mirrored inside the chunk, so the long range of one round meets the short range of the next and a pair of rounds costs every
+// workgroup the same.  An XCD still takes 32 consecutive tiles of a chunk (those of XCD 7 - x): the L2 sharing of the rectangle walk is kept.  A bijection
+// of the virtual index, so nothing downstream changes; an odd number of chunks leaves one round unpaired.
+template <bool TRI = false, bool KR = false>
 __device__ __forceinline__ TileMap map_tile(int bid, int nwg, const TileMapArgs a) {  // by value: the laboratory kernels read it from the kernel-argument address space
     {
         const int xcd = bid & 7, idx = bid >> 3;
         const int fc = (nwg >> 3) >> 5;  // full chunks of 256
         if (idx < fc * 32) {
             bid = (idx >> 5) * 256 + xcd * 32 + (idx & 31);
+            if (KR && ((idx >> 5) & 1)) bid ^= 255;  // odd chunk: backwards
         } else {
             const int rem = nwg - fc * 256, q = rem >> 3, r = rem & 7, i2 = idx - fc * 32;
             bid = fc * 256 + (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i2;

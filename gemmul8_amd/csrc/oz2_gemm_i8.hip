@@ -103,336 +103,27 @@ template <bool ZERO> struct MfmaReinitHook {  // ZERO: the start value is 0 (sho
     }
 };
 // SMALLK: the launch has K <= 512 (accumulators start at 0, three-instruction residue); the epilogue form is a compile-time property of the kernel
-template <int EPI, bool KBAR, int FUSE, bool SMALLK = false>
-__global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args, const std::conditional_t<FUSE != 0, CrtArgs, NoCrt> crt) {
-#ifndef OZ2_LAB_FUSED_CRT
-    static_assert(FUSE == 0, "the in-kernel CRT forms are laboratory code: tools/experiments/fused_crt");
-#endif
-    static_assert(FUSE == 0 || EPI == EPI_MOD, "the CRT tail follows the real requantise epilogue");
-    static_assert(offsetof(CrtArgs, Cmid) == 0 && alignof(CrtArgs) == 8, "i8_crt_tail locates the block in the kernel-argument segment");
-    (void)crt;
-    const int planes_per_tile = FUSE ? args.planes : 1;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int KT1 = args.kp / BK;    // K-steps per segment
-    const int KT = KT1 * args.nseg;  // K-steps per tile
-    const int total = args.total_tiles;
-    const int G = gridDim.x;
-
-    if (wave >= 8) {  // ------------------------------ producer waves: LDS-DMA only
-#ifdef OZ2_LAB_FUSED_CRT
-        if constexpr (KBAR && FUSE != 0) {
-            i8_producer_crt<FUSE>((__attribute__((address_space(3))) char*)smem,  // CRT on the producer waves: out of line (see there)
-                                  (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr());
-            return;
-        }
-#endif
-#include "oz2_gemm_i8_producer.inc"
-        if constexpr (KBAR) {
-        // ONE workgroup barrier per K-step (see the consumer branch).  Without per-segment barriers to pace them the producers space
-        // their instructions with s_sleep (64 clocks per unit): bursts of LDS-DMA cost (all 16 at once: +7 % kernel time).
-        for (int vb = blockIdx.x; vb < total; vb += G) {
-            for (int kt = 0; kt < KT * planes_per_tile; ++kt) {
-                const bool issued = more && OZ2_HOOK_DMA_ON(vb == (int)blockIdx.x);
-                if (issued) {
-                    PRODUCER_BEGIN();
-                    if (isB) {  // needed next K-step: 4 groups of 4 in the first part of the K-step
-#pragma unroll
-                        for (int gq = 0; gq < 4; ++gq) {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) PRODUCER_DMA(fsrc, gq * 4 + q, fdst);
-                            __builtin_amdgcn_s_sleep(OZ2_SLEEP_B);
-                        }
-                    } else {    // needed in two K-steps: 8 groups of 2 over the whole K-step
-#pragma unroll
-                        for (int gq = 0; gq < 8; ++gq) {
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) PRODUCER_DMA(fsrc, gq * 2 + q, fdst);
-                            __builtin_amdgcn_s_sleep(OZ2_SLEEP_A);
-                        }
-                    }
-                    PRODUCER_ADVANCE();
-                }
-                // the panel needed NEXT K-step must have landed: for the A producers everything except the 16 instructions just issued
-                if (!isB && issued) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-        }
-        } else {
-        for (int vb = blockIdx.x; vb < total; vb += G) {
-            for (int kt = 0; kt < KT * planes_per_tile; ++kt) {
-                // A producers: A(g+2); B producers: B(g+1); afterwards the panel needed NEXT K-step must have landed, which
-                // for the A producers means everything except the 16 instructions just issued
-                const bool issued = more && OZ2_HOOK_DMA_ON(vb == (int)blockIdx.x);
-                if (issued) PRODUCER_BEGIN();
-#pragma unroll
-                for (int sl = 0; sl < 8; ++sl) {
-                    // B (needed next K-step): 4 instructions in each of slots 0-3; A (needed in two K-steps): 2 in every slot.
-                    // Bursts cost: all 16 in slot 0 is 7 % slower than the spread issue.
-                    if (issued) {
-                        if (isB) {
-                            constexpr int PB = OZ2_PB;  // slots over which B's 16 instructions are spread
-#pragma unroll
-                            for (int q = 0; q < 16; ++q)
-                                if (q * PB / 16 == sl) PRODUCER_DMA(fsrc, q, fdst);
-                        } else {
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) PRODUCER_DMA(fsrc, sl * 2 + q, fdst);
-                        }
-                    }
-                    if (sl == 7 && issued) PRODUCER_ADVANCE();
-                    if (sl == 7) {
-                        if (!isB && issued) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    }
-                    __builtin_amdgcn_s_barrier();
-                }
-            }
-        }
-        __builtin_amdgcn_s_barrier();
-        }
-#include "oz2_gemm_i8_producer_undef.inc"
-        return;
-    }
-
-    // ------------------------------ consumer waves
-    // Matrix instruction: v_mfma_i32_16x16x64_i8 (A / B operand: lane l = row l & 15, K bytes 16 (l >> 4) .. + 15 of a 64-byte K
-    // slice; result: column l & 15, rows 4 (l >> 4) + r).  At the board's power cap it sustains 3.95-3.98 POP/s on uniformly
-    // distributed residues where v_mfma_i32_32x32x32_i8 holds 3.45 (tools/ubench/mfma_shapes.hip, profiles/archive/r02_mfma_shapes.txt):
-    // the same MACs with a quarter of the accumulator registers read and written per instruction.  Wave tile 128 x 64 = 8 x 4
-    // accumulator tiles (128 registers); a K-step (128 bytes) is four segments (K half ks2) x (row half ah) of 16 MFMAs: the B
-    // fragments of a K half are loaded in its first segment and kept for the second, the A fragments of 64 rows per segment.
-    const int wm = wave >> 2, wn = wave & 3;
-    const int r16 = lane & 15;
-    const int q = lane >> 4;
-    const int sw = (r16 >> 1) & 7;
-    const int a_base = (wm * 128 + r16) * BK;
-    const int b_base = (wn * 64 + r16) * BK;
-
-    if constexpr (KBAR) {
-    // K-step-barrier schedule: ONE workgroup barrier per K-step -- the only one the LDS ring needs (RAW: the producers' vmcnt wait for
-    // panel g + 1 precedes it; WAR: every read of K-step g precedes it, every refill of those slots follows it).  The two waves of a
-    // SIMD stay in anti-phase by construction instead of by per-segment barriers: the wm = 0 half runs L0 M0 L1 M1 L2 M2 L3 M3 inside
-    // a K-step, the wm = 1 half M3' L0 M0 L1 M1 L2 M2 L3 (M3' = the last MFMA segment of the PREVIOUS K-step, whose fragments it
-    // keeps in registers across the barrier), so one wave's LDS reads always sit beside the other's MFMAs, and when both have MFMAs
-    // ready they simply share the pipe.  The per-segment barriers of the ping-pong version cost ~7 % (every hand-over idles the
-    // matrix pipe for the barrier latency: mfma-only probe 3.70 vs 3.97 POP/s free-running).
-    __builtin_amdgcn_s_barrier();  // K-tile 0 published by the producers
-    // the whole persistent loop is instantiated once per half (WM1 = lagging half) so that each gets its own register allocation
-    auto run = [&]<bool WM1>() {
-        int sA = 0;  // slot of A(g); B(g) sits in the next slot (mod 5)
-        // MFMA_REINIT: the accumulators live across the tile loop; the v_mov initialisation runs once, every later tile finds them rewritten by
-        // the matrix pipe behind the previous epilogue (MfmaReinitHook)
-        constexpr bool MFMA_REINIT = SMALLK && EPI == EPI_MOD && FUSE == 0;  // SMALLK only: with a register C operand (start value -2^31) the form measured -0.6 ... -1.6 % at k = 1024 / 2048 (profiles/r06_short_k_epilogue_ab.txt)
-        v4i acc[8][4];
-        if constexpr (MFMA_REINIT) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = v4i{args.acc0, args.acc0, args.acc0, args.acc0};
-        }
-        for (int vb = blockIdx.x; vb < total; vb += G) {
-            const TileMap tmap = map_tile<EPI != EPI_MAX>(vb, total, args.map);
-            const PlaneRef pref = (FUSE || EPI == EPI_MAX) ? PlaneRef{0, 0} : plane_ref(args, tmap.plane);  // (the bound GEMM looks its plane up at the epilogue: one value less across its K loop)
-            const PlaneConsts pcon = (FUSE || EPI == EPI_MAX) ? PlaneConsts{} : plane_consts(args, pref);  // fetched here: the latency passes behind the K loop
-            for (int pl = 0; pl < planes_per_tile; ++pl) {
-            v4i af[4], bf[4];
-            // (Peeling the first K-step of short-K launches, its MFMAs taking the inline constant 0 as their C operand instead of the 128 v_mov_b32 per wave and
-            // tile, was tried in rounds 4 and 6: the compiler then moves seven accumulator quads through scratch INSIDE the peeled K-step, 140 bytes.  Withdrawn.)
-            if constexpr (!MFMA_REINIT) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = v4i{EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0};
-            }
-// The fragment reads of a segment are issued in the order the MFMAs use them (pinned: the scheduler otherwise issues the first-used fragment last) and the
-// waits in front of the MFMAs are the compiler's own per-fragment lgkmcnt(3..0): the first four MFMAs of a segment start when THEIR fragment has landed.  No
-// barrier covers the read latency in this schedule (in the ping-pong schedule one does: there the same change is neutral).  8192^2 x 14 planes, interleaved,
-// 25 rounds: k = 256 / 512 / 1024: +0.4 / +0.8 / +1.5 %, neutral from 2048 (profiles/r04f_kbar_partial_wait_ab.txt)
-#define OZ2_KBAR_PIN() __builtin_amdgcn_sched_barrier(0)
-#define OZ2_KBAR_WAIT() do {} while (0)
-#define OZ2_LOAD_SEG(seg_)                                                                                                   \
-    do {                                                                                                                     \
-        const int coff_ = (((((seg_) >> 1) << 2) | q) ^ sw) << 4;                                                            \
-        if (((seg_) & 1) == 0) {                                                                                             \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) bf[j] = *(const v4i*)(curB + j * 16 * BK + coff_);                 \
-        }                                                                                                                    \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) { af[i] = *(const v4i*)(curA + (((seg_) & 1) * 4 + i) * 16 * BK + coff_); OZ2_KBAR_PIN(); } \
-    } while (0)
-#define OZ2_MMA_SEG(seg_)                                                                                            \
-    do {                                                                                                                     \
-        OZ2_KBAR_WAIT();                                                                   \
-        __builtin_amdgcn_sched_barrier(0);                                                                                   \
-        __builtin_amdgcn_s_setprio(1);                                                                                       \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) {                     \
-            const int j = (i & 1) ? 3 - jj : jj; /* serpentine: see the ping-pong branch */                                   \
-            acc[((seg_) & 1) * 4 + i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[j], acc[((seg_) & 1) * 4 + i][j], 0, 0, 0); \
-        }                                                                                                                    \
-        __builtin_amdgcn_s_setprio(0);                                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    } while (0)
-#define OZ2_SET_PANELS()                                                                                                     \
-    const char* curA = smem + sA * TILE_BYTES + a_base;                                                                      \
-    const char* curB = smem + (sA == 4 ? 0 : sA + 1) * TILE_BYTES + b_base;                                                  \
-    sA = sA + 2 >= 5 ? sA - 3 : sA + 2
-            // EPI_MAX with kt_mid: two phases per tile (K-steps [0, kt_mid) and [kt_mid, KT)), the maxima epilogue after each; the
-            // accumulators run through.  Every other instantiation: one phase.
-            int kt = 0;
-            const int nph = (EPI == EPI_MAX && args.kt_mid > 0) ? 2 : 1;
-            for (int ph = 0; ph < nph; ++ph) {
-            const int kt_end = (EPI == EPI_MAX && ph + 1 < nph) ? args.kt_mid : KT;
-            auto kstep = [&]() {
-                OZ2_SET_PANELS();
-#pragma unroll
-                for (int seg = 0; seg < 4; ++seg) {
-                    OZ2_LOAD_SEG(seg);
-                    // the lagging half crosses the K-step barrier between its last LOAD and its last MFMA segment (all its LDS reads of the
-                    // K-step precede the barrier; the fragments cross it in registers): same instruction stream, shifted by one segment
-                    if (WM1 && seg == 3) {
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_sched_barrier(0);
-                        __builtin_amdgcn_s_barrier();
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    OZ2_MMA_SEG(seg);
-                }
-                if (!WM1) {
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            };
-            for (; kt < kt_end; ++kt) kstep();
-#undef OZ2_SET_PANELS
-#undef OZ2_LOAD_SEG
-#undef OZ2_MMA_SEG
-#undef OZ2_KBAR_PIN
-#undef OZ2_KBAR_WAIT
-#if OZ2_HOOK_SKIP_EPILOGUE
-            (void)tmap;  // laboratory probe: no epilogue; the accumulators stay live
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-#else
-            int lane_e = lane;
-            if constexpr (EPI == EPI_MOD) {  // (the complex combine keeps the live lane id: recomputed there, 116 bytes of accumulator spills appear in its K loop)
-            // The lane id of the epilogue is RECOMPUTED here (two v_mbcnt behind an opaque asm, so that it is not hoisted): kept live across the K loop it was
-            // spilled (12 bytes of scratch), and the reload's vmcnt(0) made every tile wait for the PREVIOUS tile's residue stores to be acknowledged --
-            // free behind a long K loop, a stall of the order of the store latency at k <= 1024 where the K loop is 2-8 us (round 6).  The consumer waves
-            // issue no other VMEM loads, so no vmcnt wait is left on their path at all.
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
-            } else {
-                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-            }
-            if constexpr (FUSE != 0) i8_epilogue<EPI, NoHook, -1>(acc, args, PlaneRef{0, pl}, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e);
-            else if constexpr (EPI == EPI_MAX) i8_epilogue<EPI, NoHook, 0>(acc, args, plane_ref(args, tmap.plane), PlaneConsts{}, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e);
-            else if constexpr (MFMA_REINIT) i8_epilogue<EPI, MfmaReinitHook<true>, (int)SMALLK>(acc, args, pref, pcon, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e, MfmaReinitHook<true>{acc, args.acc0});
-            else i8_epilogue<EPI, NoHook, (int)SMALLK>(acc, args, pref, pcon, tmap.tm * BM + (WM1 ? 128 : 0), tmap.tn * BN + wn * 64, lane_e);
-#endif
-            }  // phase
-            }
-            // FUSE: the producer waves accumulate the CRT of this tile during the next one; they read the residue planes one K-step
-            // after the barrier that follows this wait
-            if constexpr (FUSE != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        if constexpr (FUSE != 0) __builtin_amdgcn_s_barrier();  // the last tile's residues are complete: the producers drain
-    };
-    if (wm == 0) run.template operator()<false>();
-    else run.template operator()<true>();
-    } else {
-    __builtin_amdgcn_s_barrier();               // K-tile 0 published by the producers
-    if (wm == 1) __builtin_amdgcn_s_barrier();  // trailing half: one segment behind
-    int sA = 0;                                  // slot of A(g); B(g) sits in the next slot (mod 5)
-    for (int vb = blockIdx.x; vb < total; vb += G) {
-        const TileMap tmap = map_tile<EPI != EPI_MAX>(vb, total, args.map);
-        const PlaneRef pref = (FUSE || EPI == EPI_MAX) ? PlaneRef{0, 0} : plane_ref(args, tmap.plane);  // (the bound GEMM looks its plane up at the epilogue: one value less across its K loop)
-        const PlaneConsts pcon = (FUSE || EPI == EPI_MAX) ? PlaneConsts{} : plane_consts(args, pref);  // fetched here: the latency passes behind the K loop
-        for (int pl = 0; pl < planes_per_tile; ++pl) {
-        v4i acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = v4i{EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0};
-
-        int kt = 0;  // phases: see the K-step-barrier branch
-        const int nph = (EPI == EPI_MAX && args.kt_mid > 0) ? 2 : 1;
-        for (int ph = 0; ph < nph; ++ph) {
-        const int kt_end = (EPI == EPI_MAX && ph + 1 < nph) ? args.kt_mid : KT;
-        for (; kt < kt_end; ++kt) {
-            const char* curA = smem + sA * TILE_BYTES + a_base;
-            const char* curB = smem + (sA == 4 ? 0 : sA + 1) * TILE_BYTES + b_base;
-            sA = sA + 2 >= 5 ? sA - 3 : sA + 2;
-#pragma unroll
-            for (int ks2 = 0; ks2 < 2; ++ks2) {
-                const int coff = (((ks2 << 2) | q) ^ sw) << 4;
-                v4i bf[4];
-#pragma unroll
-                for (int ah = 0; ah < 2; ++ah) {
-                    v4i af[4];
-                    if (ah == 0) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            bf[j] = *(const v4i*)(curB + j * 16 * BK + coff);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        af[i] = *(const v4i*)(curA + (ah * 4 + i) * 16 * BK + coff);
-                    // Only the K-step's LAST load segment completes its reads BEFORE the barrier: that is the barrier the ring's WAR rule counts on
-                    // (LDS operations of a wave complete in order, so its wait covers every read of the K-step).  The other three segments arrive at
-                    // the barrier as soon as their reads are ISSUED and wait behind it: a wave's LDS latency no longer delays the hand-over of all
-                    // twelve (+0.4 / +0.5 % at k = 6144 / 8192, planes bit-identical: profiles/archive/r04e_late_wait_ab.txt)
-                    if (ks2 == 1 && ah == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (!(ks2 == 1 && ah == 1)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_setprio(1);
-                    // serpentine order over the 4 x 4 fragment pairs: consecutive MFMAs share an operand register also across the row change
-                    // (B fragment 3, 3, 0, 0 ...): +0.5 ... 0.65 % at k >= 8192, interleaved (profiles/archive/r04_gemm_ab_serpentine_kbar.txt)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            const int j = (i & 1) ? 3 - jj : jj;
-                            acc[ah * 4 + i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[j], acc[ah * 4 + i][j], 0, 0, 0);
-                        }
-                    __builtin_amdgcn_s_setprio(0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-#if OZ2_HOOK_SKIP_EPILOGUE
-        (void)tmap;  // laboratory probe: no epilogue; the accumulators stay live
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-#else
-        // every reload still pending on some path is waited for HERE (the previous tile's stores retired a whole K loop ago: free), so that the waitcnt
-        // pass has no reason to put a vmcnt wait into the K loop (it did, in the K-step-barrier kernels until round 4 and in the bound GEMM after a
-        // register-allocation change: tests/test_kernel_resources.py)
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-        if constexpr (FUSE != 0) i8_epilogue<EPI, NoHook, -1>(acc, args, PlaneRef{0, pl}, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane);
-        else if constexpr (EPI == EPI_MAX) i8_epilogue<EPI, NoHook, 0>(acc, args, plane_ref(args, tmap.plane), PlaneConsts{}, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane);
-        else i8_epilogue<EPI, NoHook, (int)SMALLK>(acc, args, pref, pcon, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane);
-#endif
-        }  // phase
-        }
-#ifdef OZ2_LAB_FUSED_CRT
-        if constexpr (FUSE != 0) i8_crt_tail<std::conditional_t<FUSE == 2, float, double>>(args, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane);
-#endif
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier();
-    }
-}
+#define OZ2_I8_KR 0
+#define OZ2_I8_KERNEL_HEAD                                       \
+    template <int EPI, bool KBAR, int FUSE, bool SMALLK = false> \
+    __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args, const std::conditional_t<FUSE != 0, CrtArgs, NoCrt> crt)
+#include "oz2_gemm_i8_kernel.inc"
+#undef OZ2_I8_KR
+#undef OZ2_I8_KERNEL_HEAD
+// The K-RANGED form of the same kernel (gemmul8_trmm; krange = a KRange of oz2_gemm_common.hpp, never 0): a tile runs only the K-steps [k0, k1) of its
+// range.  Producer and consumer waves derive the (scalar) range from the tile they map anyway.  The producers' panel sequence is the concatenation of the
+// tiles' ranges: kin starts at the tile's k0, PRODUCER_ADVANCE moves to the next tile at k1 -- which carries the look-ahead across the tile boundary: the
+// next tile's first panels are fetched under the current tile's last K-steps and epilogue as before --, the producers' barrier loop and the consumers' K loop
+// both run k1 - k0 steps of the tile, and the ring's slots advance per panel issued / per K-step run, so they count the K-steps actually run.  SMALLK and
+// acc0 stay launch properties derived from kp: fewer K-steps only make their bounds looser.  Residue launches of one K segment only (never the bound GEMM).
+// A kernel of its own NAME, compiled from the same text: every other launch keeps its symbol and its code (tests/test_kernel_resources.py counts them).
+#define OZ2_I8_KR 1
+#define OZ2_I8_KERNEL_HEAD                           \
+    template <int EPI, bool KBAR, int FUSE, bool SMALLK> \
+    __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kr_kernel(const GemmArgs args, const NoCrt crt, const int krange)
+#include "oz2_gemm_i8_kernel.inc"
+#undef OZ2_I8_KR
+#undef OZ2_I8_KERNEL_HEAD
 
 static void fill_common(GemmArgs& a, size_t kp, size_t m, size_t n) {
     a.kp = (int)kp;
@@ -460,15 +151,18 @@ static int num_cus() {
     return n;
 }
 
-template <int EPI, bool KBAR, int FUSE = 0, bool SMALLK = false>
-static hipError_t launch_sched(hipStream_t stream, GemmArgs& a, const std::conditional_t<FUSE != 0, CrtArgs, NoCrt>& crt = {}) {
+template <int EPI, bool KBAR, int FUSE = 0, bool SMALLK = false, bool KR = false>
+static hipError_t launch_sched(hipStream_t stream, GemmArgs& a, const std::conditional_t<FUSE != 0, CrtArgs, NoCrt>& crt = {}, [[maybe_unused]] int krange = 0) {
     // the attribute belongs to the function on ONE device; setting it is idempotent, so concurrent first calls from several host
     // threads only need the flag itself to be race-free
     static std::atomic<bool> attr_set_dev[64];
     int dev_ = 0;
     if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) dev_ = 0;
     if (!attr_set_dev[dev_].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI, KBAR, FUSE, SMALLK>, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES);
+        const void* fn;
+        if constexpr (KR) fn = (const void*)gemm_i8_kr_kernel<EPI, KBAR, FUSE, SMALLK>;
+        else fn = (const void*)gemm_i8_kernel<EPI, KBAR, FUSE, SMALLK>;
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES);
         if (e != hipSuccess) return e;
         attr_set_dev[dev_].store(true, std::memory_order_release);
     }
@@ -479,7 +173,8 @@ static hipError_t launch_sched(hipStream_t stream, GemmArgs& a, const std::condi
     if (const int want = knobs().gemm_cus; want > 0 && want < grid) grid = want;  // measurement switch (oz2_knobs.hpp): same results
     if (grid <= 0) grid = 8;
     if (a.total_tiles < grid) grid = a.total_tiles;
-    hipLaunchKernelGGL((gemm_i8_kernel<EPI, KBAR, FUSE, SMALLK>), dim3(grid), dim3(WS_THREADS), RING_LDS_BYTES, stream, a, crt);
+    if constexpr (KR) hipLaunchKernelGGL((gemm_i8_kr_kernel<EPI, KBAR, FUSE, SMALLK>), dim3(grid), dim3(WS_THREADS), RING_LDS_BYTES, stream, a, crt, krange);
+    else hipLaunchKernelGGL((gemm_i8_kernel<EPI, KBAR, FUSE, SMALLK>), dim3(grid), dim3(WS_THREADS), RING_LDS_BYTES, stream, a, crt);
     return hipGetLastError();
 }
 
@@ -489,13 +184,17 @@ static hipError_t launch_sched(hipStream_t stream, GemmArgs& a, const std::condi
 // other half's first K-steps -- overlap better) and 2.4 % slower at k = 8192, where the board is power-bound and removing stalls
 // buys nothing while the s_sleep-paced LDS-DMA is a little less smooth than the barrier-paced one.
 // tri: 0 = every tile, 1 / 2 = only the tiles of the lower / upper triangle of a square product (make_tile_map_tri; diagonal tiles whole)
-template <int EPI> static hipError_t launch(hipStream_t stream, GemmArgs& a, int planes, int tri = 0) {
+// krange (KRange, oz2_gemm_common.hpp): != 0 = every tile runs only the K-steps of its range (gemmul8_trmm; the rectangle walk, a single item)
+template <int EPI> static hipError_t launch(hipStream_t stream, GemmArgs& a, int planes, int tri = 0, int krange = 0) {
     // batched call: the items' planes are one long plane sequence (item-major), the persistent tile loop runs over all of them
     a.ppi = planes;
     a.m_ppi = map_magic((unsigned)planes);
     a.bstride = g_batch.ws;
     planes *= (int)g_batch.batch;
     if (tri != 0 && (EPI == EPI_MAX || a.tiles_m != a.tiles_n)) return hipErrorInvalidValue;
+    if (krange != 0 && (EPI == EPI_MAX || tri != 0 || a.nseg != 1 || g_batch.batch != 1 || krange < kKrALower || krange > kKrBLow)) return hipErrorInvalidValue;
+    // (the ranged operand is square: its tile count along the ranged dimension is kp / 256, which keeps every range non-empty and inside [0, KT))
+    if (krange != 0 && (krange <= kKrAUpper ? a.tiles_m : a.tiles_n) != a.kp / 256) return hipErrorInvalidValue;
     a.total_tiles = tri ? planes * (a.tiles_m * (a.tiles_m + 1) / 2) : planes * a.tiles_m * a.tiles_n;
     if (a.total_tiles <= 0) return hipSuccess;
     a.colblock = tri ? 0 : map_colblock((size_t)a.tiles_n, (size_t)a.kp * (size_t)a.nseg);  // no column blocks in the triangular walk
@@ -507,6 +206,11 @@ template <int EPI> static hipError_t launch(hipStream_t stream, GemmArgs& a, int
     // (A float-pattern accumulator form for K <= 256 -- two instead of three instructions per accumulator in the residue epilogue -- was built in round 6:
     // bit-identical, measured neutral, -1 / -2 % at 8192^2 x 128 / 256 and +1 % at 16384^2 x 256, profiles/r06_short_k_epilogue_ab.txt: retired.)
     if constexpr (EPI != EPI_MAX) {
+        if (krange != 0) {  // the same three schedules, K-ranged
+            if (a.acc0 == 0) return launch_sched<EPI, true, 0, true, true>(stream, a, {}, krange);
+            if (a.kp <= OZ2_KBAR_MAX_KP) return launch_sched<EPI, true, 0, false, true>(stream, a, {}, krange);
+            return launch_sched<EPI, false, 0, false, true>(stream, a, {}, krange);
+        }
         if (a.acc0 == 0) return launch_sched<EPI, true, 0, true>(stream, a);  // K <= 512
         if (a.kp * a.nseg <= OZ2_KBAR_MAX_KP) return launch_sched<EPI, true>(stream, a);
     }
@@ -533,7 +237,7 @@ static int nt_residue_planes(const GemmArgs& a, int planes, bool stream_out, boo
 }
 
 hipError_t launch_gemm_i8_mod(hipStream_t stream, const int8_t* A, const int8_t* B, size_t strideA, size_t strideB, size_t kp, size_t m,
-                              size_t n, int t_begin, int t_end, int8_t* out, size_t ldo, size_t strideO, bool stream_out, int tri) {
+                              size_t n, int t_begin, int t_end, int8_t* out, size_t ldo, size_t strideO, bool stream_out, int tri, int krange) {
     GemmArgs a{};
     a.A[0] = A;
     a.B[0] = B;
@@ -546,12 +250,12 @@ hipError_t launch_gemm_i8_mod(hipStream_t stream, const int8_t* A, const int8_t*
     a.strideO = strideO;
     fill_common(a, kp, m, n);
     a.nt_planes = nt_residue_planes(a, t_end - t_begin, stream_out);
-    return launch<EPI_MOD>(stream, a, t_end - t_begin, tri);
+    return launch<EPI_MOD>(stream, a, t_end - t_begin, tri, krange);
 }
 
 hipError_t launch_gemm_i8_cplx(hipStream_t stream, const int8_t* A, const int8_t* B, size_t strideA, size_t strideB, size_t kp, size_t m,
                                size_t n, int t_begin, int t_end, const int8_t* rx, const int8_t* ry, size_t strideR, int8_t* out,
-                               size_t ldo, size_t strideO, int tri) {
+                               size_t ldo, size_t strideO, int tri, int krange) {
     GemmArgs a{};
     a.A[0] = A;
     a.B[0] = B;
@@ -570,7 +274,7 @@ hipError_t launch_gemm_i8_cplx(hipStream_t stream, const int8_t* A, const int8_t
     // 2048, 7 moduli: the operand planes of the three parts never fit the Infinity Cache together, and the CRT finds more of the
     // interleaved plane there with the default policy -- so the combine launch keeps the default policy unless GEMMUL8_EPI_NT forces it)
     a.nt_planes = nt_residue_planes(a, t_end - t_begin, true, false);
-    return launch<EPI_CPLX>(stream, a, t_end - t_begin, tri);
+    return launch<EPI_CPLX>(stream, a, t_end - t_begin, tri, krange);
 }
 
 #ifndef OZ2_MAX_SMALL_TILES

@@ -18,6 +18,14 @@
 #ifndef OZ2_PRODUCER_MAP_TILE  // (the laboratory kernel that reads its arguments from the kernel-argument address space keeps the division form)
 #define OZ2_PRODUCER_MAP_TILE(vb_) map_tile<EPI != EPI_MAX>((vb_), total, args.map)
 #endif
+// Hooks of the K-ranged kernel (gemm_i8_kr_kernel defines them, oz2_gemm_i8_kernel.inc): the range [kfirst, kend) of the tile whose panels are fetched next
+// is taken where the tile is set, kin enters a tile at kfirst and PRODUCER_ADVANCE leaves it at kend.  Empty everywhere else: a tile runs [0, KT1).
+#ifndef OZ2_PRODUCER_KEND
+#define OZ2_PRODUCER_KR_DECL() do {} while (0)
+#define OZ2_PRODUCER_KR_SET(tmap_) do {} while (0)
+#define OZ2_PRODUCER_KR_ENTER() do {} while (0)
+#define OZ2_PRODUCER_KEND KT1
+#endif
 #define PRODUCER_SET_TILE(vb_)                                                                                               \
     do {                                                                                                                     \
         const TileMap tmap_ = OZ2_PRODUCER_MAP_TILE(vb_);                                                      \
@@ -35,6 +43,7 @@
             row_ = row_ < nvalid_ ? row_ : nvalid_ - 1;                                                                      \
             doff[q] = (unsigned)row_ * (unsigned)args.kp + c_ * 16;                                                          \
         }                                                                                                                    \
+        OZ2_PRODUCER_KR_SET(tmap_);                                                                                          \
     } while (0)
 #define PRODUCER_DMA(src_, q_, stage_)                                                                                       \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((src_) + doff[q_]),                     \
@@ -47,8 +56,10 @@
         int vb_next = blockIdx.x;  // tile of the panel to fetch next
         int pl_next = 0;           // FUSE: its residue plane
         bool more = true;
+        OZ2_PRODUCER_KR_DECL();
         PRODUCER_SET_TILE(vb_next);
         int seg = 0, kin = 0;      // its segment / K-step inside the segment (no divisions in the loop)
+        OZ2_PRODUCER_KR_ENTER();
         int hs = isB ? 1 : 0;      // its slot
 #define PRODUCER_BEGIN()                                                                                                     \
     do {                                                                                                                     \
@@ -58,7 +69,7 @@
 #define PRODUCER_ADVANCE()                                                                                                   \
     do {                                                                                                                     \
         hs = hs + 2 >= 5 ? hs - 3 : hs + 2;                                                                                  \
-        if (++kin == KT1) {                                                                                                  \
+        if (++kin == OZ2_PRODUCER_KEND) {                                                                                    \
             kin = 0;                                                                                                         \
             if (++seg == args.nseg) {                                                                                        \
                 seg = 0;                                                                                                     \
@@ -70,6 +81,7 @@
                     vb_next += G;                                                                                            \
                     more = vb_next < total;                                                                                  \
                     if (more) PRODUCER_SET_TILE(vb_next);                                                                    \
+                    OZ2_PRODUCER_KR_ENTER();                                                                                 \
                 }                                                                                                            \
             }                                                                                                                \
         }                                                                                                                    \

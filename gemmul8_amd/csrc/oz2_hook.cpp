@@ -16,6 +16,8 @@
 //                                                                             real beta); see try_syrk_impl
 //   hipblas{S,D,C,Z}symm(_64), hipblas{C,Z}hemm(_64)                        yes: the product with a symmetric / Hermitian matrix through gemmul8_symm / gemmul8_hemm (INT8 backend,
 //                                                                             order of A <= 2^17; one triangle of A read in place); see try_symm_impl
+//   hipblas{S,D,C,Z}trmm(_64)                                               yes: the product with a triangular matrix (ROCm 7's out-of-place signature) through gemmul8_trmm
+//                                                                             (INT8 backend, order of A <= 2^17; the triangle read in place); see try_trmm_impl
 //   hipblasLtMatmul, hipblasLtDestroy                                       yes (PyTorch's float32 matmuls): the plain case only, see lt_try
 //   hipblasLtMatrixLayoutCreate / SetAttribute / Destroy                    yes: record what a layout holds (hipBLASLt cannot be asked)
 //   rocblas_{s,d,c,z}gemm, rocblas_{s,d,c,z}gemm_strided_batched,           yes, only with GEMMUL8_HOOK_ROCBLAS=1: applications that call rocBLAS directly
@@ -34,7 +36,7 @@
 //  the rest is this build's only:
 //   GEMMUL8_FP8_BOUND, GEMMUL8_NONFINITE
 //                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace); under `ieee` SYRK / HERK / SYR2K / HER2K
-//                                              calls are not emulated (try_syrk_impl), nor are SYMM / HEMM calls (try_symm_impl)
+//                                              calls are not emulated (try_syrk_impl), nor are SYMM / HEMM (try_symm_impl) and TRMM calls (try_trmm_impl)
 //   GEMMUL8_MIN_FLOPS              per call    unset or 0 = emulate every selected call (the reference's behaviour); `auto` = a fitted cost model decides
 //                                              per call (below_floor); a number = floor on 2*m*n*k.  The first call a floor declines is logged once.
 //   GEMMUL8_DIST                   per call    blocks | moduli | fp64sum: shard every emulated GEMM over the ranks of an SPMD job (try_dist)
@@ -43,8 +45,8 @@
 //   GEMMUL8_HOOK_ROCBLAS           per call    "1" = the rocBLAS entry points above act
 //   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
 //   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call);
-//                                              a line each for hipblas{S,D,C,Z}syrk, hipblas{C,Z}herk, hipblas{S,D,C,Z}syr2k, hipblas{C,Z}her2k, hipblas{S,D,C,Z}symm and
-//                                              hipblas{C,Z}hemm when one was seen
+//                                              a line each for hipblas{S,D,C,Z}syrk, hipblas{C,Z}herk, hipblas{S,D,C,Z}syr2k, hipblas{C,Z}her2k, hipblas{S,D,C,Z}symm,
+//                                              hipblas{C,Z}hemm and hipblas{S,D,C,Z}trmm when one was seen
 //   GEMMUL8_HOOK_VERBOSE           per call    "1" = say why a hipblasLtMatmul call was left to the native routine
 //
 // Per-handle state under a mutex: three grow-only stream-ordered buffers (hipMallocAsync / hipFreeAsync), event hand-off when the handle's
@@ -71,13 +73,14 @@
 
 // The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
 // `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
-// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_her2k / gemmul8_symm / gemmul8_hemm: every such call then goes to the native routine); the shim, which binds to this
+// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_her2k / gemmul8_symm / gemmul8_hemm / gemmul8_trmm: every such call then goes to the native routine); the shim, which binds to this
 // project's own libgemmul8.so, requires every entry.
 #define OZ2_ABI(X)                                                                                          \
     X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
     X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
     X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak))) X(herk, __attribute__((weak))) \
-    X(syr2k, __attribute__((weak))) X(symm, __attribute__((weak))) X(hemm, __attribute__((weak))) X(her2k, __attribute__((weak)))
+    X(syr2k, __attribute__((weak))) X(symm, __attribute__((weak))) X(hemm, __attribute__((weak))) X(her2k, __attribute__((weak))) \
+    X(trmm, __attribute__((weak)))
 #ifndef OZ2_HOOK_SHIM
 #define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
 OZ2_ABI(X)
@@ -570,6 +573,8 @@ struct HookStats {
                                     nat_syrk_mflops[kRankKinds] = {{0}, {0}, {0}, {0}};
     // hipblas?symm [0] / hipblas?hemm [1]: 2 m n ka / 1e6 (x 4 for complex)
     std::atomic<unsigned long long> emu_symm[2] = {{0}, {0}}, nat_symm[2] = {{0}, {0}}, emu_symm_mflops[2] = {{0}, {0}}, nat_symm_mflops[2] = {{0}, {0}};
+    // hipblas?trmm: m n ka / 1e6 (x 4 for complex), the routine's own flop count
+    std::atomic<unsigned long long> emu_trmm{0}, nat_trmm{0}, emu_trmm_mflops{0}, nat_trmm_mflops{0};
     static void dump();
     HookStats() { std::atexit(&HookStats::dump); }
 };
@@ -593,6 +598,9 @@ void HookStats::dump() {
             std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu %s calls (%.3f TFLOP), native %llu %s calls through the hooked entry points (%.3f TFLOP)\n",
                          h.emu_symm[kind].load(), kSymmName[kind], h.emu_symm_mflops[kind].load() * 1e-6, h.nat_symm[kind].load(), kSymmName[kind],
                          h.nat_symm_mflops[kind].load() * 1e-6);
+    if (h.emu_trmm.load() + h.nat_trmm.load())
+        std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu TRMM calls (%.3f TFLOP), native %llu TRMM calls through the hooked entry points (%.3f TFLOP)\n",
+                     h.emu_trmm.load(), h.emu_trmm_mflops.load() * 1e-6, h.nat_trmm.load(), h.nat_trmm_mflops.load() * 1e-6);
 }
 void count_call(bool emulated, const GemmCall& c) {
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
@@ -922,6 +930,101 @@ bool try_symm(int kind, hipblasHandle_t handle, int dtype, int side, int uplo, i
         const unsigned long long mf = (unsigned long long)(2.0 * (double)m * (double)n * ka * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
         (served ? h.emu_symm : h.nat_symm)[kind].fetch_add(1, std::memory_order_relaxed);
         (served ? h.emu_symm_mflops : h.nat_symm_mflops)[kind].fetch_add(mf, std::memory_order_relaxed);
+    }
+    return served;
+}
+
+// ---- hipblas{S,D,C,Z}trmm (and the _64 twins; ROCm 7's out-of-place signature): C = alpha op(A) B / alpha B op(A) with a triangular A, through
+// gemmul8_trmm (no counterpart in the reference).  ka = the order of A (m for side = left, n for right).  Selection as for SYMM: the type's
+// GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, ka > 2^17, a moduli count outside the type's range,
+// GEMMUL8_NONFINITE=ieee (each said once), an enum value hipBLAS does not define, a dimension an int cannot hold, a library without the entry point.
+// GEMMUL8_MIN_FLOPS: a number is a floor on m n ka, the routine's own flop count; `auto` takes the GEMM model's decision for (m, n, ka) -- conservative, the
+// routine does less work than that GEMM.  The workspace (the equivalent GEMM's) grows through wC, as for SYMM.  C == B (in place) is gemmul8_trmm's contract.
+bool trmm_below_floor(int dtype, double m, double n, double ka, unsigned N, bool fast) {
+    const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
+    if (!s || !*s) return false;
+    bool declined;
+    if (s[0] == 'a' || s[0] == 'A') {
+        declined = floor_model_declines(dtype, m, n, ka, N, fast, GEMMUL8_INT8, 1.0);
+    } else {
+        const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
+        declined = f && m * n * ka < (double)f;
+    }
+    if (declined) {
+        static std::once_flag told;
+        std::call_once(told, [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cTRMM m = %.0f, n = %.0f, order of A = %.0f (%u moduli) stays on the native routine -- calls "
+                                 "below the floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], m, n, ka, N);
+        });
+    }
+    return declined;
+}
+bool try_trmm_impl(hipblasHandle_t handle, int dtype, int side, int uplo, int transA, int diag, int m, int n, const void* alpha, const void* A, int lda,
+                   const void* B, int ldb, void* C, int ldc, hipblasStatus_t* status) {
+    if (!abi().trmm) return false;
+    if ((side != HIPBLAS_SIDE_LEFT && side != HIPBLAS_SIDE_RIGHT) || (uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) ||
+        (transA != HIPBLAS_OP_N && transA != HIPBLAS_OP_T && transA != HIPBLAS_OP_C) || (diag != HIPBLAS_DIAG_NON_UNIT && diag != HIPBLAS_DIAG_UNIT))
+        return false;
+    const int ka = side == HIPBLAS_SIDE_LEFT ? m : n;
+    Selection s;
+    if (!selection_from_env(dtype, &s)) {
+        if (s.N != 0) {
+            static std::once_flag told;
+            std::call_once(told, [&] {
+                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %cTRMM calls use the native routine\n", kTypes[dtype].nmod, s.N, kTypes[dtype].max_moduli,
+                             "SDCZ"[dtype]);
+            });
+        }
+        return false;
+    }
+    if (s.backend == GEMMUL8_FP8 || ka > kMaxK) {
+        static std::once_flag told[2];  // the backend, the order of A: one notice each
+        std::call_once(told[s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] TRMM is emulated on the INT8 backend for an A of order <= %d only (GEMMUL8_BACKEND=%d, order %d): using the native "
+                                 "routine for such calls\n", kMaxK, s.backend, ka);
+        });
+        return false;
+    }
+    if (nonfinite_ieee()) {  // gemmul8_trmm ignores the non-finite mode: a NaN or Inf operand would come back as finite numbers
+        static std::once_flag told;
+        std::call_once(told, [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: TRMM has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
+                                 "for such calls\n");
+        });
+        return false;
+    }
+    if (trmm_below_floor(dtype, (double)m, (double)n, (double)ka, s.N, s.fast)) return false;
+    LockedState l = lock_ordered(handle, nullptr);
+    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
+    const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)m, (size_t)n, (size_t)ka, s.N, 0, 0, nullptr, nullptr);
+    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, "workC (trmm)"); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
+    const int rc = abi().trmm(l.stream, dtype, GEMMUL8_INT8, side, uplo, transA, diag, (size_t)m, (size_t)n, alpha, A, (size_t)lda, B, (size_t)ldb, C, (size_t)ldc,
+                              s.N, s.fast, l.sp->wC.ptr, nullptr);
+    if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
+        static std::once_flag warned;
+        std::call_once(warned, [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a TRMM call (status %d; type %d, m=%d n=%d): using the native routine for such calls\n", rc, dtype, m,
+                         n);
+        });
+        return false;
+    }
+    return *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR, true;
+}
+// counted front end; false = the native routine takes the call: also an empty product, a null pointer (the native routine reports it) or a
+// dimension an int cannot hold
+bool try_trmm(hipblasHandle_t handle, int dtype, int side, int uplo, int transA, int diag, int64_t m, int64_t n, const void* alpha, const void* A, int64_t lda,
+              const void* B, int64_t ldb, void* C, int64_t ldc, hipblasStatus_t* status) {
+    if (tl_native_depth > 0) return false;
+    const int64_t lim = 2147483647;
+    if (m <= 0 || n <= 0 || !alpha || !A || !B || !C || m > lim || n > lim || lda > lim || ldb > lim || ldc > lim) return false;
+    const bool served = try_trmm_impl(handle, dtype, side, uplo, transA, diag, (int)m, (int)n, alpha, A, (int)lda, B, (int)ldb, C, (int)ldc, status);
+    static const bool on = env_one("GEMMUL8_HOOK_STATS");
+    if (on) {
+        HookStats& h = hook_stats();
+        const double ka = side == HIPBLAS_SIDE_RIGHT ? (double)n : (double)m;
+        const unsigned long long mf = (unsigned long long)((double)m * (double)n * ka * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
+        (served ? h.emu_trmm : h.nat_trmm).fetch_add(1, std::memory_order_relaxed);
+        (served ? h.emu_trmm_mflops : h.nat_trmm_mflops).fetch_add(mf, std::memory_order_relaxed);
     }
     return served;
 }
@@ -1380,6 +1483,14 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
         if (try_symm(KIND, handle, CODE, (int)side, (int)uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;              \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc);                \
     }
+// hipblas{S,D,C,Z}trmm: ROCm 7's out-of-place signature (C may be B)
+#define OZ2_TRMM_HOOK(NAME, T, I, CODE)                                                                                                 \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasSideMode_t side, hipblasFillMode_t uplo, hipblasOperation_t transA,             \
+                         hipblasDiagType_t diag, I m, I n, const T* alpha, const T* A, I lda, const T* B, I ldb, T* C, I ldc) {         \
+        hipblasStatus_t st;                                                                                                             \
+        if (try_trmm(handle, CODE, (int)side, (int)uplo, (int)transA, (int)diag, m, n, alpha, A, lda, B, ldb, C, ldc, &st)) return st;  \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, transA, diag, m, n, alpha, A, lda, B, ldb, C, ldc);        \
+    }
 // hipblas{C,Z}her2k: a complex alpha, R = the real type of beta
 #define OZ2_HER2K_HOOK(NAME, T, R, I, CODE)                                                                                             \
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
@@ -1407,6 +1518,8 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     OZ2_SYR2K_HOOK(hipblas##U##syr2k_64, T, int64_t, CODE)                                                                              \
     OZ2_SYMM_HOOK(hipblas##U##symm, kSYMM, T, int, CODE)                                                                                \
     OZ2_SYMM_HOOK(hipblas##U##symm_64, kSYMM, T, int64_t, CODE)                                                                         \
+    OZ2_TRMM_HOOK(hipblas##U##trmm, T, int, CODE)                                                                                       \
+    OZ2_TRMM_HOOK(hipblas##U##trmm_64, T, int64_t, CODE)                                                                                \
     OZ2_ROCBLAS_HOOK(rocblas_##L##gemm, rocblas_##L##gemm_strided_batched, T, CODE)                                                     \
     OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_##L##_32, T, int, CODE,                                                                        \
                          "_Z30rocblas_internal_gemm_templateI" TAG "E15rocblas_status_P15_rocblas_handle18rocblas_operation_" Z         \
@@ -1441,6 +1554,7 @@ OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
 #undef OZ2_HERK_HOOK
 #undef OZ2_HER2K_HOOK
 #undef OZ2_SYMM_HOOK
+#undef OZ2_TRMM_HOOK
 #undef OZ2_SYR2K_HOOK
 #undef OZ2_SYRK_HOOK
 #undef OZ2_SB_HOOK

@@ -34,13 +34,15 @@ inline thread_local BatchCtx g_batch;
 
 // ---- INT8 MFMA GEMM (oz2_gemm_i8.hip)
 hipError_t launch_gemm_i8_mod(hipStream_t stream, const int8_t* A, const int8_t* B, size_t strideA, size_t strideB, size_t kp, size_t m,
-                              size_t n, int t_begin, int t_end, int8_t* out, size_t ldo, size_t strideO, bool stream_out, int tri = 0);
+                              size_t n, int t_begin, int t_end, int8_t* out, size_t ldo, size_t strideO, bool stream_out, int tri = 0, int krange = 0);
                               // stream_out: the planes are read next by the CRT pass only (non-temporal stores allowed, see the definition)
                               // tri (both launches): 1 / 2 = m == n and only the 256 x 256 tiles that touch the lower / upper triangle are computed
                               // (the triangular walk of oz2_gemm_common.hpp; the other tiles of `out` are not written)
+                              // krange (both launches; KRange in oz2_gemm_common.hpp, tri == 0): every tile runs only the K-steps in which the triangular
+                              // operand of gemmul8_trmm can be non-zero; all of `out` is written, with the bits of the full-K launch
 hipError_t launch_gemm_i8_cplx(hipStream_t stream, const int8_t* A, const int8_t* B, size_t strideA, size_t strideB, size_t kp, size_t m,
                                size_t n, int t_begin, int t_end, const int8_t* rx, const int8_t* ry, size_t strideR, int8_t* out,
-                               size_t ldo, size_t strideO, int tri = 0);
+                               size_t ldo, size_t strideO, int tri = 0, int krange = 0);
 hipError_t launch_gemm_i8_max(hipStream_t stream, int nseg, const int8_t* const* A, const int8_t* const* B, size_t kp, size_t m, size_t n,
                               int* rowmax, int* colmax, int mid_seg = 0);
 
@@ -73,7 +75,17 @@ hipError_t launch_zero(hipStream_t stream, void* p, size_t bytes);
 // stored triangle of a column-major array X: kSymLower: X[kk*ld + r] where r >= kk, else the mirrored X[r*ld + kk]; kSymUpper: X[kk*ld + r] where r <= kk,
 // else X[r*ld + kk].  herm: the mirrored half is conjugated and the stored diagonal's imaginary part counts as 0.  No element of the other strict
 // triangle is read.  Such an operand enters the kernels as a row-strided one (kmajor == false); INT8 planes, mode 0, a single GEMM.
-enum SymForm { kSymNone = 0, kSymLower = 1, kSymUpper = 2 };
+//
+// gemmul8_trmm: the TRIANGULAR form is the same descriptor with one of the kTri* bits set on kSymLower / kSymUpper (which triangle of X is stored).  Every
+// (r, kk) region of the logical operand is then one of three things: taken from the stored address X[kk*ld + r], taken from the transposed address
+// X[r*ld + kk], or ZERO without a load -- and the diagonal is the stored one or, with kTriUnit, 1 without a load:
+//   kTriStored    live half = the stored side of the diagonal at the stored address (the operand is Atri), the mirrored side is zero;
+//   kTriMirrored  live half = the mirrored side at the transposed address (the operand is Atri^T), the stored side is zero.
+// herm is not used with the triangular form; a conjugated operand (op = C) sets the operand's own `conj` flag.
+// No element of the other strict triangle of X is read in either case.
+enum SymForm { kSymNone = 0, kSymLower = 1, kSymUpper = 2, kSymBase = 3, kTriStored = 4, kTriMirrored = 8, kTriAny = 12, kTriUnit = 16 };
+// the triangular operand's live columns of row r: kk <= r (true) or kk >= r (false)
+__host__ __device__ inline bool tri_live_below(int sym) { return ((sym & kSymBase) == kSymLower) == ((sym & kTriStored) != 0); }
 // one operand of the accurate mode's extract launches; rows == 0 = absent (skip-scaling)
 struct ExtractOperand {
     bool kmajor = false, conj = false;

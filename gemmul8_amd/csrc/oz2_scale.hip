@@ -1944,8 +1944,23 @@ template <typename T> __device__ __forceinline__ T sym_conj(T v) {
     return v;
 }
 // the address rule: logical element (r, kk) of the operand (sym == kSymNone: the plain row-strided element)
+template <typename T> __device__ __forceinline__ T sym_one() {
+    T v = ET<T>::zero();
+    if constexpr (ET<T>::cplx) v.x = 1;
+    else v = 1;
+    return v;
+}
 template <typename T> __device__ __forceinline__ T sym_at(const T* X, size_t ld, size_t r, size_t kk, int sym, int herm) {
-    const bool stored = sym == kSymNone || (sym == kSymLower ? r >= kk : r <= kk);
+    const int base = sym & kSymBase;
+    const bool stored = base == kSymNone || (base == kSymLower ? r >= kk : r <= kk);
+    if (sym & kTriAny) {  // triangular form (gemmul8_trmm): the dead half and a unit diagonal without a load
+        if (r == kk) {
+            if (sym & kTriUnit) return sym_one<T>();
+        } else if (stored != ((sym & kTriStored) != 0)) {
+            return ET<T>::zero();
+        }
+        return (sym & kTriStored) ? X[kk * ld + r] : X[r * ld + kk];  // (op = C: the operand's own `conj` flag, applied where the planes are written)
+    }
     T v = stored ? X[kk * ld + r] : X[r * ld + kk];
     if constexpr (ET<T>::cplx) {
         if (herm) {
@@ -1978,12 +1993,15 @@ template <typename T, int MODE> __device__ __forceinline__ void stage_sym_body(c
     const size_t r0 = (size_t)rt * TR, kb = (size_t)kt * TK;
     const T* const X = (const T*)((const char*)a.X + OZ2_ZX);
     const size_t ld = a.ld;
-    enum { TILE_STORED = 0, TILE_MIRRORED = 1, TILE_DIAGONAL = 2 };
+    enum { TILE_STORED = 0, TILE_MIRRORED = 1, TILE_DIAGONAL = 2, TILE_DEAD = 3 };
     int cls = TILE_STORED;
     if (a.sym != kSymNone) {  // (uniform)
         const bool above = r0 + TR - 1 < kb, below = r0 > kb + TK - 1;  // every r < every kk / every r > every kk of the tile
-        const bool lower = a.sym == kSymLower;
+        const bool lower = (a.sym & kSymBase) == kSymLower;
         cls = (lower ? below : above) ? TILE_STORED : (lower ? above : below) ? TILE_MIRRORED : TILE_DIAGONAL;
+        // triangular form: a tile strictly on the dead side of the diagonal is zero WITHOUT a load; the emit pass below writes its plane bytes (the
+        // bytes of zeros: the planes of the whole operand are written by this launch, nothing relies on an earlier fill)
+        if ((a.sym & kTriAny) && cls != TILE_DIAGONAL && (cls == TILE_STORED) != ((a.sym & kTriStored) != 0)) cls = TILE_DEAD;
     }
     if constexpr (MODE == MODE_BOUND) {  // row maxima of the tile's rows = the maximum over the k splits' partial arrays (amax_sym_pair_kernel)
         constexpr int PL = 256 / TR;
@@ -2003,7 +2021,9 @@ template <typename T, int MODE> __device__ __forceinline__ void stage_sym_body(c
         }
         if (pp == 0) rowam[rr] = v;
     }
-    if (cls == TILE_MIRRORED) {
+    if (cls == TILE_DEAD) {
+        for (int i = threadIdx.x; i < TR * TK; i += 256) tile[i / TK][i % TK] = E::zero();
+    } else if (cls == TILE_MIRRORED) {
         constexpr int EPV = sizeof(T) >= 16 ? 1 : 16 / (int)sizeof(T);  // elements per 16-byte piece
         constexpr int VPR = TK / EPV;                                   // pieces per tile row
         constexpr int NV = TR * VPR / 256;                              // pieces per thread (4 for every type)
@@ -2165,8 +2185,14 @@ template <typename T> __device__ __forceinline__ void amax_sym_body(const AmaxSy
     const size_t kper = (k + o.parts - 1) / o.parts;
     const size_t kbeg = (size_t)by * kper, kend = (kbeg + kper < k) ? kbeg + kper : k;
     size_t sb, se, mb, me;  // columns read along the rows [sb, se) / along kk [mb, me)
-    if (o.sym == kSymLower) sb = kbeg, se = kend < R0 + 64 ? kend : R0 + 64, mb = kbeg > R0 + 64 ? kbeg : R0 + 64, me = kend;
+    if ((o.sym & kSymBase) == kSymLower) sb = kbeg, se = kend < R0 + 64 ? kend : R0 + 64, mb = kbeg > R0 + 64 ? kbeg : R0 + 64, me = kend;
     else mb = kbeg, me = kend < R0 ? kend : R0, sb = kbeg > R0 ? kbeg : R0, se = kend;
+    if (o.sym & kTriStored) {  // triangular form: the mirrored side of all 64 rows is zero -- not read (a maximum does not notice a zero)
+        me = mb;
+    } else if (o.sym & kTriMirrored) {  // the stored side is zero: only the columns the diagonal crosses in these 64 rows go through the address rule
+        if ((o.sym & kSymBase) == kSymLower) sb = sb > R0 ? sb : R0;
+        else se = se < R0 + 64 ? se : R0 + 64;
+    }
     auto take = [](const T& v, U& am) {
         const U ar = (U)fabs(E::re(v)), ai = (U)fabs(E::im(v));
         am = ar > am ? ar : am;
@@ -2255,9 +2281,18 @@ __device__ __forceinline__ void fast_shift_sym_body(const T* X, size_t ld, size_
             sum[j] = sqr_add_ru<U>(ai, sum[j]);
         }
     };
+    // Triangular form (gemmul8_trmm): an element the plain kernel reads as an explicit zero of the materialised matrix adds nothing to this lane's sums --
+    // max(a, 0) = a, and the round-up sum of a non-negative s and 0 * 0 is s exactly (x + 0 == x) --, so the columns that are dead for ALL rows of the
+    // block are not visited at all (the code relies on that identity there); inside the visited range a dead element enters the same lane's sum, in its
+    // place, as the zero sym_at returns without a load.  The live elements keep their lane (column mod 32) and their ascending order.
+    size_t cbeg = 0, cend = k;
+    if (sym & kTriAny) {
+        if (tri_live_below(sym)) cend = row0 + RPL < k ? row0 + RPL : k;  // live: kk <= r
+        else cbeg = row0 / 32 * 32;                                        // live: kk >= r
+    }
     if (row0 < rows) {
-        size_t col = ty;
-        for (; col + 7 * 32 < k; col += 8 * 32) {
+        size_t col = cbeg + ty;
+        for (; col + 7 * 32 < cend; col += 8 * 32) {
             T v[8][RPL];
 #pragma unroll
             for (int u = 0; u < 8; ++u)
@@ -2268,7 +2303,7 @@ __device__ __forceinline__ void fast_shift_sym_body(const T* X, size_t ld, size_
 #pragma unroll
                 for (int j = 0; j < RPL; ++j) take(v[u][j], j);
         }
-        for (; col < k; col += 32) {
+        for (; col < cend; col += 32) {
 #pragma unroll
             for (int j = 0; j < RPL; ++j)
                 if (row0 + j < rows) take(sym_at<T>(X, ld, row0 + j, col, sym, herm), j);
@@ -2305,7 +2340,10 @@ template <typename T> __global__ void __launch_bounds__(256) fast_shift_sym_pair
 // a symmetric-form operand is square (rows == k), row-strided, on INT8 planes, in a single GEMM; its partner is any general operand
 static bool sym_operand_ok(int sym, bool herm, bool kmajor, size_t rows, size_t k, int dtype) {
     if (sym == kSymNone) return !herm;
-    return (sym == kSymLower || sym == kSymUpper) && !kmajor && rows == k && (!herm || is_complex(dtype));
+    const int base = sym & kSymBase, tri = sym & kTriAny;
+    if ((sym & ~(kSymBase | kTriAny | kTriUnit)) || (tri != 0 && tri != kTriStored && tri != kTriMirrored) || (tri == 0 && (sym & kTriUnit)) || (tri != 0 && herm))
+        return false;
+    return (base == kSymLower || base == kSymUpper) && !kmajor && rows == k && (!herm || is_complex(dtype));
 }
 template <typename T> static hipError_t launch_amax_sym_pair_t(hipStream_t stream, size_t k, const ExtractOperand& A, const ExtractOperand& B) {
     auto mk = [](const ExtractOperand& o) {

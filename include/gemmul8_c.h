@@ -270,6 +270,39 @@ GEMMUL8_API int gemmul8_hemm(void *stream, int dtype, int backend, int side, int
                              size_t lda, const void *B, size_t ldb, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
                              void *work, double *timers_ns);
 
+/* Product with a triangular matrix: C = alpha*op(A)*B (side = LEFT, A is m x m) or C = alpha*B*op(A) (side = RIGHT, A is n x n); B and C are m x n,
+ * ka = the order of A.  All four types; transA is N, T or C (0 / 1 / 2 or the hipblasOperation_t values 111 / 112 / 113; for the real types C is T), side
+ * and uplo as in gemmul8_symm, diag GEMMUL8_NON_UNIT / GEMMUL8_UNIT or the hipblasDiagType_t values 131 / 132.  alpha is of the element type, host or
+ * device, detected as elsewhere; there is no beta.  INT8 backend only (GEMMUL8_FP8: GEMMUL8_E_UNSUPPORTED -- the FP6 panel writer has no triangular form).
+ *   - The materialised matrix: Atri is the ka x ka matrix BLAS defines -- the stored entries of the triangle named by uplo, exact zeros in the other strict
+ *     triangle and, under GEMMUL8_UNIT, ones on the diagonal (the stored diagonal is then not read).  M = op(Atri), conjugated for C; Mt is the plain
+ *     transpose of M.  No byte of the other strict triangle of A, of the lda padding or, under UNIT, of the diagonal is ever read: a NaN there reaches
+ *     nothing.  Neither Atri nor M is ever materialised: the scaling kernels read A through the triangle, in place, and take the other half as zero
+ *     without a load.
+ *   - Bit identity: the whole m x n window of C holds, bit for bit, what gemmul8_gemm puts there in non-finite mode 0 on the INT8 backend with M
+ *     materialised --
+ *       LEFT:   gemmul8_gemm(dtype, GEMMUL8_INT8, N, N, m, n, m, alpha, M, ka, B, ldb, 0, C, ldc, ...);
+ *       RIGHT:  gemmul8_gemm(dtype, GEMMUL8_INT8, N, T, m, n, n, alpha, B, ldb, Mt, ka, 0, C, ldc, ...).
+ *     Stated this way for gemmul8_symm's reason: on either side and for every transA the triangular operand enters the scaling kernels in the
+ *     ROW-STRIDED form, so the fast mode's round-up sums have one lane order to reproduce.  An element the plain kernel reads as an explicit zero of M
+ *     either enters the same lane's sum in its place as a zero (produced without a load) or, where a column is zero for every row a workgroup handles,
+ *     is absent from it: the sums are of non-negative terms rounded up, and x + 0 == x holds for them exactly.
+ *   - The residue GEMMs run, for every 256 x 256 tile, only the 128-wide K-steps in which the tile's rows (LEFT) or columns (RIGHT) of M can hold a
+ *     non-zero; a product of residues of zeros adds exactly 0 to an int32 accumulator, so no bit of the residue planes changes.
+ *   - `work` holds gemmul8_work_size(is_complex, GEMMUL8_INT8, m, n, ka, num_moduli, 0, 0, NULL, NULL) bytes: the equivalent GEMM's workspace.
+ *   - C is never read (its incoming bytes do not matter); no byte of the ldc padding is written; A is never written.  C == B with ldc == ldb is allowed
+ *     -- the in-place form of classic BLAS: B is read in the scaling phase only and C is written by the CRT only, in stream order.  Any other overlap of
+ *     C with A or B is the caller's error.
+ *   - m == 0 or n == 0: GEMMUL8_OK, C untouched.  Bad side / uplo / transA / diag, a null pointer, ka > 2^17, dtype or backend out of range:
+ *     GEMMUL8_E_ARG, answered before any HIP call; num_moduli out of the type's range: GEMMUL8_E_NUM_MODULI.
+ *   - timers_ns, stream order and capture safety (timers_ns == NULL) as in gemmul8_gemm.
+ *   - gemmul8_set_nonfinite_mode is ignored: the call behaves as mode 0.
+ * No counterpart in the reference (it emulates GEMM only). */
+enum { GEMMUL8_NON_UNIT = 0, GEMMUL8_UNIT = 1 };
+GEMMUL8_API int gemmul8_trmm(void *stream, int dtype, int backend, int side, int uplo, int transA, int diag, size_t m, size_t n, const void *alpha,
+                             const void *A, size_t lda, const void *B, size_t ldb, void *C, size_t ldc, unsigned num_moduli, int fastmode, void *work,
+                             double *timers_ns);
+
 /* D(i, j) += bias[i] for a column-major m x n real matrix: the broadcast bias of a hipblasLtMatmul BIAS epilogue, applied by the hook after
  * the emulated GEMM (one more rounding than the vendor's fused form).  S / D only.  No counterpart in the reference. */
 GEMMUL8_API int gemmul8_add_row_bias(void *stream, int dtype, size_t m, size_t n, void *D, size_t ldd, const void *bias);
