@@ -39,7 +39,7 @@ _lib = None
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
            "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
            "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk", "gemmul8_syr2k",
-           "gemmul8_symm", "gemmul8_hemm", "gemmul8_her2k", "gemmul8_trmm"]
+           "gemmul8_symm", "gemmul8_hemm", "gemmul8_her2k", "gemmul8_trmm", "gemmul8_trsm", "gemmul8_trsm_work_size", "gemmul8_trsm_leaf"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
 
@@ -140,6 +140,13 @@ def bind(L):
     L.gemmul8_trmm.restype = C.c_int
     L.gemmul8_trmm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    L.gemmul8_trsm.restype = C.c_int
+    L.gemmul8_trsm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                               C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    L.gemmul8_trsm_work_size.restype = C.c_size_t
+    L.gemmul8_trsm_work_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint]
+    L.gemmul8_trsm_leaf.restype = C.c_int
+    L.gemmul8_trsm_leaf.argtypes = []
     L.gemmul8_set_fp8_bound_mode.restype = C.c_int
     L.gemmul8_set_fp8_bound_mode.argtypes = [C.c_int]
     L.gemmul8_set_nonfinite_mode.restype = C.c_int
@@ -447,6 +454,53 @@ def trmm(A, B, num_moduli, side="L", uplo="L", trans="N", diag="N", alpha=1, fas
                             B.data_ptr(), B.stride(0), C_out.data_ptr(), C_out.stride(0), num_moduli, int(fastmode), work.data_ptr(), tm)
     check(rc, "gemmul8_trmm")
     return C_out, (list(tm) if timers else None), work
+
+
+def trsm_work_size(is_complex, m, n, side, num_moduli):
+    """Bytes of workspace gemmul8_trsm needs: the largest workspace of the recipe's GEMMs, rounded up to 64, plus a 64-byte tail."""
+    return lib().gemmul8_trsm_work_size(int(is_complex), INT8, SIDE[side], m, n, num_moduli)
+
+
+def trsm(A, B, num_moduli, side="L", uplo="L", trans="N", diag="N", alpha=1, fastmode=False, work=None, stream=None, timers=False):
+    """Solves op(A) X = alpha*B (side "L", A is m x m) or X op(A) = alpha*B (side "R", A is n x n) with a TRIANGULAR A through gemmul8_trsm, IN PLACE: B
+    is overwritten with X.  Only the triangle `uplo` of A is read -- under diag "U" not even its diagonal; trans "N" / "T" / "C".  INT8 backend.  The
+    result is the recipe include/gemmul8_c.h states (tests/trsm_util.py is its model): a recursive blocking whose updates are `gemm` calls on sub-matrix
+    views and whose diagonal blocks of order <= TRSM_LEAF are solved by substitution in the element type.  alpha: a number, or a one-element device tensor
+    of A's dtype.  A and B are column-major matrices held as tensors of shape (cols, rows), as in `gemm`; views with a larger leading dimension are taken
+    through tensor.stride(0).  Returns (B, timers_ns or None, work); timers_ns[2] is the time of the leaf solves."""
+    import numpy as np
+    import torch
+    dt = A.dtype
+    for X in (A, B):
+        assert X.is_cuda and X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]
+    if B.dtype != dt or A.shape[0] != A.shape[1]:
+        raise TypeError("A and B must share one dtype, A must be square, and every column must be contiguous")
+    n, m = B.shape
+    ka = m if SIDE[side] == 0 else n
+    if A.shape[0] != ka:
+        raise ValueError(f"A is of order {A.shape[0]}, side {side!r} of an {m} x {n} B needs {ka}")
+    if work is None:
+        work = torch.empty(trsm_work_size(dt.is_complex, m, n, side, num_moduli), dtype=torch.uint8, device=A.device)
+    if isinstance(alpha, torch.Tensor):
+        if not alpha.is_cuda or alpha.dtype != dt or alpha.numel() != 1:
+            raise TypeError("a tensor alpha is one element of A's dtype on the device")
+        al_ptr = alpha.data_ptr()
+    else:
+        np_dt = {torch.float32: np.float32, torch.float64: np.float64, torch.complex64: np.complex64, torch.complex128: np.complex128}[dt]
+        al = np.array([alpha], dtype=np_dt)
+        al_ptr = al.ctypes.data
+    tm = (C.c_double * 4)() if timers else None
+    st = stream if stream is not None else torch.cuda.current_stream(A.device).cuda_stream
+    rc = lib().gemmul8_trsm(st, _dtype_code(dt), INT8, SIDE[side], UPLO[uplo], OPS[trans], DIAG[diag], m, n, al_ptr, A.data_ptr(), A.stride(0),
+                            B.data_ptr(), B.stride(0), num_moduli, int(fastmode), work.data_ptr(), tm)
+    check(rc, "gemmul8_trsm")
+    return B, (list(tm) if timers else None), work
+
+
+def __getattr__(name):
+    if name == "TRSM_LEAF":  # the leaf order of gemmul8_trsm, read from the library
+        return lib().gemmul8_trsm_leaf()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def gemm_batched(A, B, num_moduli, fastmode=False, opA="N", opB="N", alpha=1.0, beta=0.0, C_out=None, work=None, stream=None, backend=INT8):

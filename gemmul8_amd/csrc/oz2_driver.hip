@@ -1034,6 +1034,156 @@ int gemmul8_trmm(void* stream_, int dtype, int backend, int side, int uplo, int 
     return trmm((hipStream_t)stream_, dtype, backend, side, uplo, transA, diag, m, n, alpha, A, lda, B, ldb, C, ldc, N, fastmode, work, timers_ns);
 }
 
+// ---- triangular solve (no counterpart in the reference): op(A) X = alpha B / X op(A) = alpha B, X over B.  The result is the recipe of
+// include/gemmul8_c.h, bit for bit: a recursion over the diagonal blocks of M = op(Atri) that halves at h = the largest L 2^j strictly below the block's
+// order, solves one half, updates the other with ONE gemmul8_gemm on sub-matrix views (alpha = -1; beta = the caller's alpha while that scale is still
+// pending for those elements, else 1) and solves it; blocks of order <= L go to the leaf kernel (oz2_trsm.hip).  The off-diagonal block of M is a
+// rectangle inside the stored triangle and is read where it lies, through op = transA.  TrsmCtx carries one call; walk() is also the workspace rule (gemms
+// only, nothing launched).
+struct TrsmCtx {
+    hipStream_t stream;
+    int dtype, transA;
+    bool left, lowerA, lowerM, unit, alpha_dev;
+    size_t nrhs, lda, ldb, esz;
+    const char* A;
+    char* B;
+    const void *alpha, *minus_one, *one;
+    unsigned N;
+    int fastmode;
+    void* work;
+    double* timers;  // the caller's four slots, or nullptr
+    Timer* T;
+    size_t max_work;  // walk(): the largest GEMM workspace
+    bool dry;
+};
+// element (i, j) of M in the stored array
+static inline const char* trsm_m_at(const TrsmCtx& c, size_t i, size_t j) { return c.A + (c.transA == 0 ? j * c.lda + i : i * c.lda + j) * c.esz; }
+static int trsm_leaf_call(TrsmCtx& c, size_t d0, size_t r, bool scaled) {
+    if (c.dry) return GEMMUL8_OK;
+    char* Bb = c.B + (c.left ? d0 : d0 * c.ldb) * c.esz;
+    if (c.T) OZ2_HIP(hipEventRecord(c.T->ev[0], c.stream));
+    OZ2_HIP(launch_trsm_leaf(c.stream, c.dtype, c.left, c.lowerA, c.transA, c.unit, (unsigned)r, c.nrhs, trsm_m_at(c, d0, d0), c.lda, Bb, c.ldb, scaled, c.alpha,
+                             c.alpha_dev));
+    if (c.T) {
+        OZ2_HIP(hipEventRecord(c.T->ev[1], c.stream));
+        OZ2_HIP(hipEventSynchronize(c.T->ev[1]));
+        float ms;
+        OZ2_HIP(hipEventElapsedTime(&ms, c.T->ev[0], c.T->ev[1]));
+        c.timers[2] += ms * 1e6;
+    }
+    return GEMMUL8_OK;
+}
+// B[dst block] = -M[dst, src] X[src] + beta B[dst block] (left) or -X[src] M[src, dst] + beta B[dst block] (right); blocks given as (first index, order)
+static int trsm_update(TrsmCtx& c, size_t src0, size_t nsrc, size_t dst0, size_t ndst, bool scaled) {
+    const size_t gm = c.left ? ndst : c.nrhs, gn = c.left ? c.nrhs : ndst;
+    if (c.dry) {
+        // the size does not know uplo / transA: M lower and M upper have the same blocks with source and destination exchanged
+        const size_t gm2 = c.left ? nsrc : c.nrhs, gn2 = c.left ? c.nrhs : nsrc;
+        c.max_work = std::max({c.max_work, gemmul8_work_size(is_complex(c.dtype), kINT8, gm, gn, nsrc, c.N, 0, 0, nullptr, nullptr),
+                               gemmul8_work_size(is_complex(c.dtype), kINT8, gm2, gn2, ndst, c.N, 0, 0, nullptr, nullptr)});
+        return GEMMUL8_OK;
+    }
+    const void* beta = scaled ? c.alpha : c.one;
+    double tm[4];
+    int rc;
+    if (c.left)
+        rc = gemmul8_gemm(c.stream, c.dtype, kINT8, c.transA, 0, gm, gn, nsrc, c.minus_one, trsm_m_at(c, dst0, src0), c.lda, c.B + src0 * c.esz, c.ldb, beta,
+                          c.B + dst0 * c.esz, c.ldb, c.N, c.fastmode, c.work, nullptr, nullptr, 0, 0, 0, 0, c.timers ? tm : nullptr);
+    else
+        rc = gemmul8_gemm(c.stream, c.dtype, kINT8, 0, c.transA, gm, gn, nsrc, c.minus_one, c.B + src0 * c.ldb * c.esz, c.ldb, trsm_m_at(c, src0, dst0), c.lda, beta,
+                          c.B + dst0 * c.ldb * c.esz, c.ldb, c.N, c.fastmode, c.work, nullptr, nullptr, 0, 0, 0, 0, c.timers ? tm : nullptr);
+    if (rc) return rc;
+    if (c.timers) c.timers[0] += tm[0], c.timers[1] += tm[1], c.timers[3] += tm[3];
+    return GEMMUL8_OK;
+}
+static int trsm_walk(TrsmCtx& c, size_t d0, size_t r, bool scaled) {
+    const size_t L = (size_t)trsm_leaf_order();
+    if (r <= L) return trsm_leaf_call(c, d0, r, scaled);
+    size_t h = L;
+    while (2 * h < r) h *= 2;  // the largest L 2^j strictly below r
+    // the half solved first: block 1 when the substitution runs forwards (left and M lower, right and M upper), else block 2
+    const bool first_is_1 = c.left == c.lowerM;
+    const size_t f0 = first_is_1 ? d0 : d0 + h, fn = first_is_1 ? h : r - h, s0 = first_is_1 ? d0 + h : d0, sn = first_is_1 ? r - h : h;
+    int rc = trsm_walk(c, f0, fn, scaled);
+    if (rc) return rc;
+    rc = trsm_update(c, f0, fn, s0, sn, scaled);
+    if (rc) return rc;
+    return trsm_walk(c, s0, sn, false);
+}
+static int trsm_norm(int& side, int& uplo, int& transA, int& diag) {
+    if (side == 141) side = GEMMUL8_LEFT;  // hipblasSideMode_t
+    else if (side == 142) side = GEMMUL8_RIGHT;
+    if (uplo == 122) uplo = GEMMUL8_LOWER;  // hipblasFillMode_t
+    else if (uplo == 121) uplo = GEMMUL8_UPPER;
+    if (diag == 131) diag = GEMMUL8_NON_UNIT;  // hipblasDiagType_t
+    else if (diag == 132) diag = GEMMUL8_UNIT;
+    transA = norm_op(transA);
+    return (side != GEMMUL8_LEFT && side != GEMMUL8_RIGHT) || (uplo != GEMMUL8_LOWER && uplo != GEMMUL8_UPPER) || transA < 0 || transA > 2 ||
+                   (diag != GEMMUL8_NON_UNIT && diag != GEMMUL8_UNIT)
+               ? GEMMUL8_E_ARG
+               : GEMMUL8_OK;
+}
+
+int gemmul8_trsm_leaf(void) { return trsm_leaf_order(); }
+
+size_t gemmul8_trsm_work_size(int is_cplx, int backend, int side, size_t m, size_t n, unsigned N) {
+    if (side == 141) side = GEMMUL8_LEFT;
+    else if (side == 142) side = GEMMUL8_RIGHT;
+    TrsmCtx c{};
+    c.dtype = is_cplx ? kC64 : kF64;  // (the GEMM workspace depends on complex or not only)
+    c.left = side != GEMMUL8_RIGHT, c.lowerM = true;
+    c.nrhs = c.left ? n : m;
+    c.N = N;
+    c.dry = true;
+    (void)backend;  // INT8 only: the size is that backend's
+    if (m && n) (void)trsm_walk(c, 0, c.left ? m : n, true);
+    return (c.max_work + 63) / 64 * 64 + 64;
+}
+
+int gemmul8_trsm(void* stream_, int dtype, int backend, int side, int uplo, int transA, int diag, size_t m, size_t n, const void* alpha, const void* A, size_t lda,
+                 void* B, size_t ldb, unsigned N, int fastmode, void* work, double* timers_ns) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (timers_ns) timers_ns[0] = timers_ns[1] = timers_ns[2] = timers_ns[3] = 0.0;
+    if (dtype < 0 || dtype > 3 || backend < 0 || backend > 1) return GEMMUL8_E_ARG;
+    if (trsm_norm(side, uplo, transA, diag)) return GEMMUL8_E_ARG;
+    if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
+    if (!alpha || !A || !B || !work) return GEMMUL8_E_ARG;
+    const size_t ka = side == GEMMUL8_LEFT ? m : n;
+    if (ka > (size_t(1) << 17)) return GEMMUL8_E_ARG;
+    if (backend == kFP8) return GEMMUL8_E_UNSUPPORTED;
+    if (m == 0 || n == 0) return GEMMUL8_OK;
+    TrsmCtx c{};
+    c.stream = stream, c.dtype = dtype, c.transA = transA;
+    c.left = side == GEMMUL8_LEFT, c.lowerA = uplo == GEMMUL8_LOWER, c.lowerM = c.lowerA == (transA == 0), c.unit = diag == GEMMUL8_UNIT;
+    c.nrhs = c.left ? n : m, c.lda = lda, c.ldb = ldb, c.esz = (is_f32(dtype) ? 4 : 8) * (is_complex(dtype) ? 2 : 1);
+    c.A = (const char*)A, c.B = (char*)B, c.alpha = alpha, c.N = N, c.fastmode = fastmode, c.work = work, c.timers = timers_ns;
+    c.alpha_dev = scalars_on_device(alpha);
+    // the constants of the GEMMs live where alpha lives
+    const float cf[2][2] = {{-1.0f, 0.0f}, {1.0f, 0.0f}};
+    const double cd[2][2] = {{-1.0, 0.0}, {1.0, 0.0}};
+    if (c.alpha_dev) {
+        // the 64-byte tail behind the GEMMs' workspace, written in stream order (capture-safe)
+        c.dry = true;
+        (void)trsm_walk(c, 0, ka, true);
+        c.dry = false;
+        char* tail = (char*)(((uintptr_t)work + (c.max_work + 63) / 64 * 64 + 15) & ~uintptr_t(15));
+        OZ2_HIP(launch_trsm_consts(stream, dtype, tail));
+        c.minus_one = tail, c.one = tail + 16;
+    } else {
+        c.minus_one = is_f32(dtype) ? (const void*)cf[0] : (const void*)cd[0];
+        c.one = is_f32(dtype) ? (const void*)cf[1] : (const void*)cd[1];
+        // BLAS: alpha == 0 sets X = 0 and does not reference A
+        const bool zero = is_f32(dtype) ? ((const float*)alpha)[0] == 0.0f && (!is_complex(dtype) || ((const float*)alpha)[1] == 0.0f)
+                                        : ((const double*)alpha)[0] == 0.0 && (!is_complex(dtype) || ((const double*)alpha)[1] == 0.0);
+        if (zero) {
+            OZ2_HIP(launch_trsm_zero_fill(stream, dtype, m, n, B, ldb));
+            return GEMMUL8_OK;
+        }
+    }
+    c.T = timers_ns ? thread_timer() : nullptr;
+    return trsm_walk(c, 0, ka, true);
+}
+
 int gemmul8_add_f64(void* stream_, double* dst, const double* src, size_t count) {
     if (!dst || !src || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15)) return GEMMUL8_E_ARG;
     OZ2_HIP(launch_add_f64((hipStream_t)stream_, dst, src, count));

@@ -18,6 +18,8 @@
 //                                                                             order of A <= 2^17; one triangle of A read in place); see try_symm_impl
 //   hipblas{S,D,C,Z}trmm(_64)                                               yes: the product with a triangular matrix (ROCm 7's out-of-place signature) through gemmul8_trmm
 //                                                                             (INT8 backend, order of A <= 2^17; the triangle read in place); see try_trmm_impl
+//   hipblas{S,D,C,Z}trsm(_64)                                               yes: the triangular solve, in place on B, through gemmul8_trsm (INT8 backend, order of A
+//                                                                             <= 2^17; recursive blocking, emulated GEMM updates); see try_trsm_impl
 //   hipblasLtMatmul, hipblasLtDestroy                                       yes (PyTorch's float32 matmuls): the plain case only, see lt_try
 //   hipblasLtMatrixLayoutCreate / SetAttribute / Destroy                    yes: record what a layout holds (hipBLASLt cannot be asked)
 //   rocblas_{s,d,c,z}gemm, rocblas_{s,d,c,z}gemm_strided_batched,           yes, only with GEMMUL8_HOOK_ROCBLAS=1: applications that call rocBLAS directly
@@ -36,7 +38,7 @@
 //  the rest is this build's only:
 //   GEMMUL8_FP8_BOUND, GEMMUL8_NONFINITE
 //                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace); under `ieee` SYRK / HERK / SYR2K / HER2K
-//                                              calls are not emulated (try_syrk_impl), nor are SYMM / HEMM (try_symm_impl) and TRMM calls (try_trmm_impl)
+//                                              calls are not emulated (try_syrk_impl), nor are SYMM / HEMM (try_symm_impl), TRMM (try_trmm_impl) and TRSM calls (try_trsm_impl)
 //   GEMMUL8_MIN_FLOPS              per call    unset or 0 = emulate every selected call (the reference's behaviour); `auto` = a fitted cost model decides
 //                                              per call (below_floor); a number = floor on 2*m*n*k.  The first call a floor declines is logged once.
 //   GEMMUL8_DIST                   per call    blocks | moduli | fp64sum: shard every emulated GEMM over the ranks of an SPMD job (try_dist)
@@ -46,7 +48,7 @@
 //   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
 //   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call);
 //                                              a line each for hipblas{S,D,C,Z}syrk, hipblas{C,Z}herk, hipblas{S,D,C,Z}syr2k, hipblas{C,Z}her2k, hipblas{S,D,C,Z}symm,
-//                                              hipblas{C,Z}hemm and hipblas{S,D,C,Z}trmm when one was seen
+//                                              hipblas{C,Z}hemm, hipblas{S,D,C,Z}trmm and hipblas{S,D,C,Z}trsm when one was seen
 //   GEMMUL8_HOOK_VERBOSE           per call    "1" = say why a hipblasLtMatmul call was left to the native routine
 //
 // Per-handle state under a mutex: three grow-only stream-ordered buffers (hipMallocAsync / hipFreeAsync), event hand-off when the handle's
@@ -73,14 +75,14 @@
 
 // The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
 // `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
-// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_her2k / gemmul8_symm / gemmul8_hemm / gemmul8_trmm: every such call then goes to the native routine); the shim, which binds to this
+// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_her2k / gemmul8_symm / gemmul8_hemm / gemmul8_trmm / gemmul8_trsm: every such call then goes to the native routine); the shim, which binds to this
 // project's own libgemmul8.so, requires every entry.
 #define OZ2_ABI(X)                                                                                          \
     X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
     X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
     X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak))) X(herk, __attribute__((weak))) \
     X(syr2k, __attribute__((weak))) X(symm, __attribute__((weak))) X(hemm, __attribute__((weak))) X(her2k, __attribute__((weak))) \
-    X(trmm, __attribute__((weak)))
+    X(trmm, __attribute__((weak))) X(trsm, __attribute__((weak))) X(trsm_work_size, __attribute__((weak)))
 #ifndef OZ2_HOOK_SHIM
 #define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
 OZ2_ABI(X)
@@ -575,6 +577,8 @@ struct HookStats {
     std::atomic<unsigned long long> emu_symm[2] = {{0}, {0}}, nat_symm[2] = {{0}, {0}}, emu_symm_mflops[2] = {{0}, {0}}, nat_symm_mflops[2] = {{0}, {0}};
     // hipblas?trmm: m n ka / 1e6 (x 4 for complex), the routine's own flop count
     std::atomic<unsigned long long> emu_trmm{0}, nat_trmm{0}, emu_trmm_mflops{0}, nat_trmm_mflops{0};
+    // hipblas?trsm: m n ka / 1e6 (x 4 for complex)
+    std::atomic<unsigned long long> emu_trsm{0}, nat_trsm{0}, emu_trsm_mflops{0}, nat_trsm_mflops{0};
     static void dump();
     HookStats() { std::atexit(&HookStats::dump); }
 };
@@ -601,6 +605,9 @@ void HookStats::dump() {
     if (h.emu_trmm.load() + h.nat_trmm.load())
         std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu TRMM calls (%.3f TFLOP), native %llu TRMM calls through the hooked entry points (%.3f TFLOP)\n",
                      h.emu_trmm.load(), h.emu_trmm_mflops.load() * 1e-6, h.nat_trmm.load(), h.nat_trmm_mflops.load() * 1e-6);
+    if (h.emu_trsm.load() + h.nat_trsm.load())
+        std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu TRSM calls (%.3f TFLOP), native %llu TRSM calls through the hooked entry points (%.3f TFLOP)\n",
+                     h.emu_trsm.load(), h.emu_trsm_mflops.load() * 1e-6, h.nat_trsm.load(), h.nat_trsm_mflops.load() * 1e-6);
 }
 void count_call(bool emulated, const GemmCall& c) {
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
@@ -1025,6 +1032,104 @@ bool try_trmm(hipblasHandle_t handle, int dtype, int side, int uplo, int transA,
         const unsigned long long mf = (unsigned long long)((double)m * (double)n * ka * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
         (served ? h.emu_trmm : h.nat_trmm).fetch_add(1, std::memory_order_relaxed);
         (served ? h.emu_trmm_mflops : h.nat_trmm_mflops).fetch_add(mf, std::memory_order_relaxed);
+    }
+    return served;
+}
+
+// ---- hipblas{S,D,C,Z}trsm (and the _64 twins): op(A) X = alpha B / X op(A) = alpha B, X over B, through gemmul8_trsm (no counterpart in the reference).
+// Selection and the ways to the native routine as for TRMM: the FP8 backend, ka > 2^17, a moduli count outside the type's range, GEMMUL8_NONFINITE=ieee (each
+// said once), an enum value hipBLAS does not define, a dimension an int cannot hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: a number is a
+// floor on m n ka; `auto` declines below the order kTrsmAutoMinOrder.  The workspace (gemmul8_trsm_work_size) grows through wC.
+//
+// kTrsmAutoMinOrder: the smallest measured order of A from which the emulated routine beats the native one at n = ka in float64 accurate mode
+// (profiles/trsm_ab.json, tools/trsm_ab.py; INTEGRATION.md "TRSM" prints the table): DTRSM left at 14 moduli loses at 8192 x 8192 (25.1 against 19.4 ms) and
+// wins at 16384 x 16384 (88.6 against 108.1 ms).  The rule asks for the order only: it also declines the right-side 8192 x 8192 row, which the emulation wins.
+constexpr int kTrsmAutoMinOrder = 16384;
+bool trsm_below_floor(int dtype, double m, double n, double ka, unsigned N) {
+    const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
+    if (!s || !*s) return false;
+    bool declined;
+    if (s[0] == 'a' || s[0] == 'A') {
+        declined = ka < (double)kTrsmAutoMinOrder;
+    } else {
+        const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
+        declined = f && m * n * ka < (double)f;
+    }
+    if (declined) {
+        static std::once_flag told;
+        std::call_once(told, [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cTRSM m = %.0f, n = %.0f, order of A = %.0f (%u moduli) stays on the native routine -- calls "
+                                 "below the floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], m, n, ka, N);
+        });
+    }
+    return declined;
+}
+bool try_trsm_impl(hipblasHandle_t handle, int dtype, int side, int uplo, int transA, int diag, int m, int n, const void* alpha, const void* A, int lda, void* B,
+                   int ldb, hipblasStatus_t* status) {
+    if (!abi().trsm || !abi().trsm_work_size) return false;
+    if ((side != HIPBLAS_SIDE_LEFT && side != HIPBLAS_SIDE_RIGHT) || (uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) ||
+        (transA != HIPBLAS_OP_N && transA != HIPBLAS_OP_T && transA != HIPBLAS_OP_C) || (diag != HIPBLAS_DIAG_NON_UNIT && diag != HIPBLAS_DIAG_UNIT))
+        return false;
+    const int ka = side == HIPBLAS_SIDE_LEFT ? m : n;
+    Selection s;
+    if (!selection_from_env(dtype, &s)) {
+        if (s.N != 0) {
+            static std::once_flag told;
+            std::call_once(told, [&] {
+                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %cTRSM calls use the native routine\n", kTypes[dtype].nmod, s.N, kTypes[dtype].max_moduli,
+                             "SDCZ"[dtype]);
+            });
+        }
+        return false;
+    }
+    if (s.backend == GEMMUL8_FP8 || ka > kMaxK) {
+        static std::once_flag told[2];  // the backend, the order of A: one notice each
+        std::call_once(told[s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] TRSM is emulated on the INT8 backend for an A of order <= %d only (GEMMUL8_BACKEND=%d, order %d): using the native "
+                                 "routine for such calls\n", kMaxK, s.backend, ka);
+        });
+        return false;
+    }
+    if (nonfinite_ieee()) {  // gemmul8_trsm ignores the non-finite mode: its GEMM updates would turn a NaN or Inf operand into finite numbers
+        static std::once_flag told;
+        std::call_once(told, [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: TRSM has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
+                                 "for such calls\n");
+        });
+        return false;
+    }
+    if (trsm_below_floor(dtype, (double)m, (double)n, (double)ka, s.N)) return false;
+    LockedState l = lock_ordered(handle, nullptr);
+    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
+    const size_t need = abi().trsm_work_size(kTypes[dtype].cplx, GEMMUL8_INT8, side, (size_t)m, (size_t)n, s.N);
+    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, "workC (trsm)"); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
+    const int rc = abi().trsm(l.stream, dtype, GEMMUL8_INT8, side, uplo, transA, diag, (size_t)m, (size_t)n, alpha, A, (size_t)lda, B, (size_t)ldb, s.N, s.fast,
+                              l.sp->wC.ptr, nullptr);
+    if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
+        static std::once_flag warned;
+        std::call_once(warned, [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a TRSM call (status %d; type %d, m=%d n=%d): using the native routine for such calls\n", rc, dtype, m,
+                         n);
+        });
+        return false;
+    }
+    return *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR, true;
+}
+// counted front end; false = the native routine takes the call: also an empty call, a null pointer (the native routine reports it) or a dimension an int
+// cannot hold
+bool try_trsm(hipblasHandle_t handle, int dtype, int side, int uplo, int transA, int diag, int64_t m, int64_t n, const void* alpha, const void* A, int64_t lda,
+              void* B, int64_t ldb, hipblasStatus_t* status) {
+    if (tl_native_depth > 0) return false;
+    const int64_t lim = 2147483647;
+    if (m <= 0 || n <= 0 || !alpha || !A || !B || m > lim || n > lim || lda > lim || ldb > lim) return false;
+    const bool served = try_trsm_impl(handle, dtype, side, uplo, transA, diag, (int)m, (int)n, alpha, A, (int)lda, B, (int)ldb, status);
+    static const bool on = env_one("GEMMUL8_HOOK_STATS");
+    if (on) {
+        HookStats& h = hook_stats();
+        const double ka = side == HIPBLAS_SIDE_RIGHT ? (double)n : (double)m;
+        const unsigned long long mf = (unsigned long long)((double)m * (double)n * ka * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
+        (served ? h.emu_trsm : h.nat_trsm).fetch_add(1, std::memory_order_relaxed);
+        (served ? h.emu_trsm_mflops : h.nat_trsm_mflops).fetch_add(mf, std::memory_order_relaxed);
     }
     return served;
 }
@@ -1491,6 +1596,14 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
         if (try_trmm(handle, CODE, (int)side, (int)uplo, (int)transA, (int)diag, m, n, alpha, A, lda, B, ldb, C, ldc, &st)) return st;  \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, transA, diag, m, n, alpha, A, lda, B, ldb, C, ldc);        \
     }
+// hipblas{S,D,C,Z}trsm: in place on B
+#define OZ2_TRSM_HOOK(NAME, T, I, CODE)                                                                                                 \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasSideMode_t side, hipblasFillMode_t uplo, hipblasOperation_t transA,             \
+                         hipblasDiagType_t diag, I m, I n, const T* alpha, const T* A, I lda, T* B, I ldb) {                            \
+        hipblasStatus_t st;                                                                                                             \
+        if (try_trsm(handle, CODE, (int)side, (int)uplo, (int)transA, (int)diag, m, n, alpha, A, lda, B, ldb, &st)) return st;          \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, transA, diag, m, n, alpha, A, lda, B, ldb);                \
+    }
 // hipblas{C,Z}her2k: a complex alpha, R = the real type of beta
 #define OZ2_HER2K_HOOK(NAME, T, R, I, CODE)                                                                                             \
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
@@ -1520,6 +1633,8 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     OZ2_SYMM_HOOK(hipblas##U##symm_64, kSYMM, T, int64_t, CODE)                                                                         \
     OZ2_TRMM_HOOK(hipblas##U##trmm, T, int, CODE)                                                                                       \
     OZ2_TRMM_HOOK(hipblas##U##trmm_64, T, int64_t, CODE)                                                                                \
+    OZ2_TRSM_HOOK(hipblas##U##trsm, T, int, CODE)                                                                                       \
+    OZ2_TRSM_HOOK(hipblas##U##trsm_64, T, int64_t, CODE)                                                                                \
     OZ2_ROCBLAS_HOOK(rocblas_##L##gemm, rocblas_##L##gemm_strided_batched, T, CODE)                                                     \
     OZ2_ROCBLAS_INTERNAL(oz2_rb_int_gemm_##L##_32, T, int, CODE,                                                                        \
                          "_Z30rocblas_internal_gemm_templateI" TAG "E15rocblas_status_P15_rocblas_handle18rocblas_operation_" Z         \
@@ -1555,6 +1670,7 @@ OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
 #undef OZ2_HER2K_HOOK
 #undef OZ2_SYMM_HOOK
 #undef OZ2_TRMM_HOOK
+#undef OZ2_TRSM_HOOK
 #undef OZ2_SYR2K_HOOK
 #undef OZ2_SYRK_HOOK
 #undef OZ2_SB_HOOK

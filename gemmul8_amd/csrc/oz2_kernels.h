@@ -200,6 +200,17 @@ hipError_t launch_crt_tri(hipStream_t stream, int dtype, unsigned N, size_t n, i
 hipError_t launch_crt_her2k(hipStream_t stream, int dtype, unsigned N, size_t n, int tri, const void* Cmid, size_t ld_mid, size_t plane_stride,
                             const int16_t* sftA, const int16_t* sftB, const void* alpha, const void* beta, bool scalars_on_device, void* C, size_t ldc);
 
+// ---- gemmul8_trsm (oz2_trsm.hip): the leaf solve of one diagonal block of M = op(Atri), of order r <= trsm_leaf_order(), against nrhs right-hand sides, in
+// place.  A: element (0, 0) of the block in the stored array; B: the block's first row (left) or first column (!left) of the window.  scaled: every element
+// of B is multiplied by alpha (host value or device pointer) before anything else.  Only the stored triangle lower_a of the block is addressed, and under
+// `unit` not its diagonal.
+int trsm_leaf_order();
+hipError_t launch_trsm_leaf(hipStream_t stream, int dtype, bool left, bool lower_a, int transA, bool unit, unsigned r, size_t nrhs, const void* A, size_t lda,
+                            void* B, size_t ldb, bool scaled, const void* alpha, bool alpha_on_device);
+// -1 at tail, +1 at tail + 16 bytes, in the element type: the scalars of gemmul8_trsm's GEMMs beside a device-resident alpha
+hipError_t launch_trsm_consts(hipStream_t stream, int dtype, void* tail);
+hipError_t launch_trsm_zero_fill(hipStream_t stream, int dtype, size_t m, size_t n, void* B, size_t ldb);  // +0 over the m x n window
+
 hipError_t launch_row_bias(hipStream_t stream, int dtype, size_t m, size_t n, void* D, size_t ldd, const void* bias);
 hipError_t launch_add_f64(hipStream_t stream, double* dst, const double* src, size_t count);  // dst += src (16-byte aligned arrays)
 

@@ -303,6 +303,46 @@ GEMMUL8_API int gemmul8_trmm(void *stream, int dtype, int backend, int side, int
                              const void *A, size_t lda, const void *B, size_t ldb, void *C, size_t ldc, unsigned num_moduli, int fastmode, void *work,
                              double *timers_ns);
 
+/* Solve with a triangular matrix, in place: op(A) X = alpha B (side = LEFT, A is m x m) or X op(A) = alpha B (side = RIGHT, A is n x n); B is m x n and is
+ * overwritten with X -- the in-place form of BLAS; ka = the order of A.  All four types; side, uplo, transA, diag and their spellings as in gemmul8_trmm;
+ * alpha is of the element type.  INT8 backend only (GEMMUL8_FP8: GEMMUL8_E_UNSUPPORTED).  ka <= 2^17.
+ *   - The result is a recipe, bit for bit.  M = op(Atri) (Atri: the stored triangle; under GEMMUL8_UNIT its diagonal is not read and counts as ones; transA = C
+ *     conjugates an entry as it is read) is never materialised; M is lower triangular iff (uplo == LOWER) == (transA == N).  L = gemmul8_trsm_leaf().
+ *     solve(M, Bblk, s) on a diagonal block of order r, with a pending scale s (the caller's alpha, or none):
+ *       r <= L: the leaf solve below.  Otherwise h = the largest L * 2^j strictly below r, M11 is h x h, and B splits the same way (rows: LEFT, columns: RIGHT):
+ *         LEFT,  M lower:  X1 = solve(M11, B1, s);  B2 = gemm(-1 * M21 * X1 + beta * B2);  X2 = solve(M22, B2, none)
+ *         LEFT,  M upper:  X2 = solve(M22, B2, s);  B1 = gemm(-1 * M12 * X2 + beta * B1);  X1 = solve(M11, B1, none)
+ *         RIGHT, M upper:  X1 first;  B2 = gemm(-1 * X1 * M12 + beta * B2);  then X2
+ *         RIGHT, M lower:  X2 first;  B1 = gemm(-1 * X2 * M21 + beta * B1);  then X1
+ *       beta = s where a scale is pending, else 1: the scale reaches every element of B exactly once, at its first touch.  Every gemm is gemmul8_gemm
+ *       (GEMMUL8_INT8, this call's num_moduli and fastmode, non-finite mode 0) on the sub-matrix views; the off-diagonal block of M -- a rectangle inside the
+ *       stored triangle -- is read where it lies in A, through op = transA.
+ *     The leaf solve (order r <= L, one right-hand side; LEFT, M lower):
+ *         for i = 0 .. r-1:  acc = s (x) b_i  (no scale pending: acc = b_i);  for j = 0 .. i-1 ascending: acc = acc (-) (m_ij (x) x_j);
+ *                            x_i = acc (UNIT)  or  acc (/) m_ii (NON_UNIT)
+ *       LEFT, M upper: i descending, j descending from r-1 to i+1.  RIGHT, M upper: x_j = (s b_j - sum_{i<j} x_i m_ij) / m_jj, j and i ascending.  RIGHT, M
+ *       lower: both descending.  Every (x), (-), (/) is ONE correctly rounded IEEE operation of the element type; nothing is contracted into an FMA.  Complex
+ *       types: the product is the textbook four products and two sums (ar*br - ai*bi, ar*bi + ai*br); the quotient is the textbook
+ *       den = dr*dr + di*di; ((ar*dr + ai*di) / den, (ai*dr - ar*di) / den), each operation rounded once -- NOT scaled against overflow: unsafe for |m_ii|
+ *       outside about 2^+-500 (Z) / 2^+-60 (C).  tests/trsm_util.py is this recipe in Python.
+ *   - Bytes never read: no byte of the other strict triangle of A, of the lda padding or, under UNIT, of the diagonal -- a NaN there reaches nothing.
+ *   - Bytes never written: A is never written; no byte of B outside the m x n window is written.  B must not overlap A.
+ *   - alpha lives on the host or on the device, detected as elsewhere.  A HOST alpha equal to zero sets the window to +0 without reading A, as BLAS does.  A
+ *     DEVICE alpha takes the recipe as it stands (a zero there multiplies: a NaN or Inf of B or A propagates); the constants -1 and 1 the GEMMs need beside
+ *     it are written by a kernel, in stream order, into the 64-byte tail of `work`.
+ *   - `work` holds gemmul8_trsm_work_size(is_complex, GEMMUL8_INT8, side, m, n, num_moduli) bytes: the maximum of gemmul8_work_size over the recipe's GEMMs
+ *     (over both orientations of M: the size does not ask for uplo / transA), rounded up to a multiple of 64, plus the 64-byte tail.
+ *   - timers_ns: four doubles; slots 0 / 1 / 3 are summed over the GEMMs, slot 2 holds the leaf solves (the slot that is always 0 elsewhere); one host
+ *     synchronisation per GEMM and per leaf.  NULL: fully asynchronous and capture-safe.
+ *   - A zero on a non-unit diagonal gives Inf / NaN, as IEEE division gives; nothing is checked.
+ *   - m == 0 or n == 0: GEMMUL8_OK, nothing touched.  Argument errors and their order as in gemmul8_trmm, answered before any HIP call.
+ *   - gemmul8_set_nonfinite_mode is ignored: the GEMMs behave as mode 0.
+ * No counterpart in the reference (it emulates GEMM only). */
+GEMMUL8_API size_t gemmul8_trsm_work_size(int is_complex, int backend, int side, size_t m, size_t n, unsigned num_moduli);
+GEMMUL8_API int gemmul8_trsm_leaf(void); /* the leaf order L: 64 or 128, a build-time constant */
+GEMMUL8_API int gemmul8_trsm(void *stream, int dtype, int backend, int side, int uplo, int transA, int diag, size_t m, size_t n, const void *alpha,
+                             const void *A, size_t lda, void *B, size_t ldb, unsigned num_moduli, int fastmode, void *work, double *timers_ns);
+
 /* D(i, j) += bias[i] for a column-major m x n real matrix: the broadcast bias of a hipblasLtMatmul BIAS epilogue, applied by the hook after
  * the emulated GEMM (one more rounding than the vendor's fused form).  S / D only.  No counterpart in the reference. */
 GEMMUL8_API int gemmul8_add_row_bias(void *stream, int dtype, size_t m, size_t n, void *D, size_t ldd, const void *bias);
