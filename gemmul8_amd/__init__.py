@@ -39,7 +39,8 @@ _lib = None
 EXPORTS = ["gemmul8_version", "gemmul8_work_size", "gemmul8_gemm", "gemmul8_get_layout", "gemmul8_scale",
            "gemmul8_scale_bounds", "gemmul8_scale_finish", "gemmul8_lowprec_gemm", "gemmul8_crt", "gemmul8_set_fp8_bound_mode", "gemmul8_set_nonfinite_mode",
            "gemmul8_hook_would_emulate", "gemmul8_reload_knobs", "gemmul8_abi_version", "gemmul8_layout_bytes", "gemmul8_syrk", "gemmul8_herk", "gemmul8_syr2k",
-           "gemmul8_symm", "gemmul8_hemm", "gemmul8_her2k", "gemmul8_trmm", "gemmul8_trsm", "gemmul8_trsm_work_size", "gemmul8_trsm_leaf"]
+           "gemmul8_symm", "gemmul8_hemm", "gemmul8_her2k", "gemmul8_trmm", "gemmul8_trsm", "gemmul8_trsm_work_size", "gemmul8_trsm_leaf",
+           "gemmul8_gemm_batched_ptr"]
 
 ABI_VERSION = 7  # GEMMUL8_ABI_VERSION of include/gemmul8_c.h this module's struct mirrors were written against
 
@@ -122,6 +123,10 @@ def bind(L):
     L.gemmul8_gemm_batched.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_longlong, C.c_void_p, C.c_size_t, C.c_longlong, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_longlong, C.c_size_t, C.c_uint, C.c_int, C.c_void_p]
+    L.gemmul8_gemm_batched_ptr.restype = C.c_int
+    L.gemmul8_gemm_batched_ptr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint,
+                                           C.c_int, C.c_void_p]
     L.gemmul8_syrk.restype = C.c_int
     L.gemmul8_syrk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
@@ -532,3 +537,71 @@ def gemm_batched(A, B, num_moduli, fastmode=False, opA="N", opB="N", alpha=1.0, 
                                     int(fastmode), work.data_ptr())
     check(rc, "gemmul8_gemm_batched")
     return C_out, work
+
+
+def gemm_batched_ptr(As, Bs, num_moduli, fastmode=False, opA="N", opB="N", alpha=1.0, beta=0.0, Cs=None, work=None, stream=None, backend=INT8,
+                     m=None, n=None, k=None, lda=None, ldb=None, ldc=None, dtype=None):
+    """A pointer-array batch as ONE set of launches (gemmul8_gemm_batched_ptr): item b is Cs[b] = alpha op(As[b]) op(Bs[b]) + beta Cs[b].
+
+    As, Bs, Cs: sequences of `batch` tensors, each operand's of one shape, dtype and leading dimension -- column-major matrices held as tensors of shape
+    (cols, rows) as in `gemm`; views (tensor.stride(0) is the leading dimension), scattered allocations and the same tensor repeated are all fine for As and
+    Bs; the Cs must not overlap.  Cs=None allocates the outputs.  The three device arrays of addresses are built with one host-to-device copy per operand,
+    allocated and copied ON THE STREAM THE CALL RUNS ON (`stream`: a raw stream handle, default torch's current stream): the copies are ordered before the
+    kernels that read the arrays, and the allocator hands their memory out again only to later work of that stream.
+
+    Alternatively As, Bs, Cs are int64 device tensors of `batch` addresses each (nothing is copied; the kernels read them in stream order, under graph
+    capture at every replay); m, n, k, lda, ldb, ldc and dtype are then given explicitly.
+
+    Returns (Cs, work).  Bit-identical to calling `gemm` per item.  Item addresses are not validated."""
+    import numpy as np
+    import torch
+    if isinstance(As, torch.Tensor) != isinstance(Bs, torch.Tensor) or (Cs is not None and isinstance(Cs, torch.Tensor) != isinstance(As, torch.Tensor)):
+        raise TypeError("As, Bs and Cs are all sequences of tensors or all int64 device tensors of addresses")
+    if isinstance(As, torch.Tensor):
+        if Cs is None or None in (m, n, k, lda, ldb, ldc, dtype):
+            raise TypeError("address tensors need Cs, m, n, k, lda, ldb, ldc and dtype")
+        for X in (As, Bs, Cs):
+            if not (X.is_cuda and X.dtype == torch.int64 and X.dim() == 1 and X.is_contiguous() and X.numel() == As.numel()):
+                raise TypeError("address arrays are contiguous one-dimensional int64 device tensors of one length")
+        dt, batch, dev = dtype, As.numel(), As.device
+        pa, pb, pc = As, Bs, Cs
+        call_stream = torch.cuda.ExternalStream(stream, device=dev) if stream is not None else torch.cuda.current_stream(dev)
+    else:
+        As, Bs = list(As), list(Bs)
+        batch = len(As)
+        if batch == 0 or len(Bs) != batch:
+            raise ValueError("As and Bs hold the same number (>= 1) of items")
+        dt, dev = As[0].dtype, As[0].device
+        call_stream = torch.cuda.ExternalStream(stream, device=dev) if stream is not None else torch.cuda.current_stream(dev)
+
+        def common(Xs, what):
+            for X in Xs:
+                if not (X.is_cuda and X.device == dev and X.dtype == dt and X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= X.shape[1] and
+                        X.shape == Xs[0].shape and X.stride(0) == Xs[0].stride(0)):
+                    raise TypeError(f"the items of {what} are device matrices of one dtype, shape and leading dimension with contiguous columns")
+            return Xs[0].shape, Xs[0].stride(0)
+        (ca, ra), lda = common(As, "As")
+        (cb, rb), ldb = common(Bs, "Bs")
+        m, k = (ra, ca) if opA == "N" else (ca, ra)
+        kb, n = (rb, cb) if opB == "N" else (cb, rb)
+        if k != kb:
+            raise ValueError(f"inner dimensions differ: {k} and {kb}")
+        if Cs is None:
+            Cs = [torch.zeros((n, m), dtype=dt, device=dev) for _ in range(batch)]
+        Cs = list(Cs)
+        if len(Cs) != batch:
+            raise ValueError("Cs holds one tensor per item")
+        (cc, rc_), ldc = common(Cs, "Cs")
+        if (cc, rc_) != (n, m):
+            raise ValueError(f"the items of Cs are {(cc, rc_)}, the products are {(n, m)}")
+        # one host-to-device copy per operand, on the call's stream
+        with torch.cuda.stream(call_stream):
+            pa, pb, pc = [torch.tensor([X.data_ptr() for X in Xs], dtype=torch.int64).to(dev) for Xs in (As, Bs, Cs)]
+    if work is None:
+        work = torch.empty(lib().gemmul8_work_size_batched(int(dt.is_complex), backend, m, n, k, num_moduli, batch), dtype=torch.uint8, device=dev)
+    np_dt = {torch.float32: np.float32, torch.float64: np.float64, torch.complex64: np.complex64, torch.complex128: np.complex128}[dt]
+    al, be = np.array([alpha], dtype=np_dt), np.array([beta], dtype=np_dt)
+    rc = lib().gemmul8_gemm_batched_ptr(call_stream.cuda_stream, _dtype_code(dt), backend, OPS[opA], OPS[opB], m, n, k, al.ctypes.data, pa.data_ptr(), lda, pb.data_ptr(), ldb,
+                                        be.ctypes.data, pc.data_ptr(), ldc, batch, num_moduli, int(fastmode), work.data_ptr())
+    check(rc, "gemmul8_gemm_batched_ptr")
+    return Cs, work

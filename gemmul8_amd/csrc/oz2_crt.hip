@@ -104,7 +104,7 @@ __device__ __forceinline__ void crt_load(const CrtArgs& a, const CrtPos& p, size
 }
 
 // TRI (crt_tri_kernel): only the entries of the triangle a.tri names are read and stored -- a unit that the diagonal cuts moves element by element
-template <typename U, bool CPLX, typename MID, int LB, bool LDS_STORE, int NMAX, bool TRI = false>
+template <typename U, bool CPLX, typename MID, int LB, bool LDS_STORE, int NMAX, bool TRI = false, bool PTR = false>
 __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size_t gid, size_t total, unsigned row_groups,
                                          const typename CrtVec<MID, LB, (CPLX ? 2 : 1)>::Vec (&c)[NMAX], char* stage) {
     constexpr int COMPS = CPLX ? 2 : 1;
@@ -133,7 +133,7 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
     }
     const int16_t* sftA_z = (const int16_t*)((const char*)a.sftA + zw);
     const int sB = (int)((const int16_t*)((const char*)a.sftB + zw))[col];
-    U* Cc = (U*)((char*)a.C + blockIdx.z * a.bc) + (col * a.ldc) * COMPS;
+    U* Cc = (U*)crt_item_c<PTR>(a) + (col * a.ldc) * COMPS;
     auto stored = [&](size_t row) { return row < a.m && (!TRI || (a.tri == 1 ? row >= col : row <= col)); };
     const bool full = i0 + ROWS <= a.m && (!TRI || (a.tri == 1 ? i0 >= col : i0 + ROWS - 1 <= col));  // all ROWS rows exist (and are stored): the old and new C values move as one vector per thread
     const bool beta0 = be[0] == (U)0 && (!CPLX || be[1] == (U)0);
@@ -222,7 +222,7 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
         const size_t first = gid - lane, last = first + 63;
         const size_t colf = first / row_groups;
         const size_t i0f = (first - colf * row_groups) * ROWS;
-        char* wdst = (char*)((U*)((char*)a.C + blockIdx.z * a.bc) + (colf * a.ldc + i0f) * COMPS);
+        char* wdst = (char*)((U*)crt_item_c<PTR>(a) + (colf * a.ldc + i0f) * COMPS);
         const bool wave_fast = last < total && last / row_groups == colf && i0f + (size_t)64 * ROWS <= a.m && ((uintptr_t)wdst & 15u) == 0 &&
                                (!TRI || (a.tri == 1 ? i0f >= colf : i0f + (size_t)64 * ROWS - 1 <= colf));
         if (wave_fast) {
@@ -252,7 +252,9 @@ __device__ __forceinline__ void crt_unit(const CrtArgs& a, const CrtPos& p, size
 #ifndef OZ2_CRT_WAVES
 #define OZ2_CRT_WAVES 4  // waves per SIMD the register allocation aims at (experiment switch)
 #endif
-template <typename U, bool CPLX, typename MID, int LB, int UNITS, int NMAX>
+// PTR = true: the instantiation a pointer-array batch runs (gemmul8_gemm_batched_ptr): item z's C is a.pc[z].  (A template parameter and not a shared
+// inlined body: the kernel written as a wrapper around one compiles to other code than the kernel itself.)
+template <typename U, bool CPLX, typename MID, int LB, int UNITS, int NMAX, bool PTR = false>
 __global__ void __launch_bounds__(OZ2_CRT_BLOCK) __attribute__((amdgpu_waves_per_eu(OZ2_CRT_WAVES, 8))) crt_kernel(const CrtArgs a) {
     constexpr int COMPS = CPLX ? 2 : 1;
     constexpr int ROWS = LB / (COMPS * (int)sizeof(MID));  // LB = 8: 8 / 4 / 4 / 2 rows; wider vectors cost registers
@@ -277,7 +279,7 @@ __global__ void __launch_bounds__(OZ2_CRT_BLOCK) __attribute__((amdgpu_waves_per
             pos[(u + 1) & 1] = crt_pos<ROWS>(gid + OZ2_CRT_BLOCK, total, row_groups);
             crt_load<MID, LB, COMPS, NMAX>(a, pos[(u + 1) & 1], gid + OZ2_CRT_BLOCK, cb[(u + 1) & 1]);
         }
-        crt_unit<U, CPLX, MID, LB, LDS_STORE, NMAX>(a, pos[u & 1], gid, total, row_groups, cb[u & 1], stage);
+        crt_unit<U, CPLX, MID, LB, LDS_STORE, NMAX, false, PTR>(a, pos[u & 1], gid, total, row_groups, cb[u & 1], stage);
     }
 }
 
@@ -685,8 +687,9 @@ hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, si
     fill_crt_scalars(a, dtype, alpha, beta, scalars_on_device);
     a.bw = g_batch.ws;
     a.bc = g_batch.sc;
+    a.pc = g_batch.pc;
     const bool cplx = is_complex(dtype), i8 = backend == kINT8;
-    {
+    if (!g_batch.pc) {  // (a pointer array: the items' alignment is not the host's to know -- the register form, which tests every address it stores to)
         // LDS-DMA form: int8 residues, whole 1024-byte units per column, 16-byte aligned slices and C columns
         const size_t comps = cplx ? 2 : 1, usz = is_f32(dtype) ? 4 : 8;
         const int force = knobs().crt_kernel;  // 1 = dma, 2 = reg: testing switch (default: dma when eligible and large enough)
@@ -715,7 +718,9 @@ hipError_t launch_crt(hipStream_t stream, int dtype, int backend, unsigned N, si
     dim3 grid((unsigned)((threads + OZ2_CRT_BLOCK - 1) / OZ2_CRT_BLOCK), 1, g_batch.batch);  // one unit per thread
 #define OZ2_CRT(U, CP, MID)                                                                                                      \
     do {                                                                                                                         \
-        if (N > 14) hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 20>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);             \
+        if (a.pc && N > 14) hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 20, true>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);  \
+        else if (a.pc) hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 14, true>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);       \
+        else if (N > 14) hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 20>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);        \
         else hipLaunchKernelGGL((crt_kernel<U, CP, MID, OZ2_CRT_LB, 1, 14>), grid, dim3(OZ2_CRT_BLOCK), 0, stream, a);                    \
     } while (0)
     if (i8) {

@@ -27,7 +27,15 @@ struct CrtArgs {
     int tri;        // crt_tri_kernel: 1 = only entries i >= j, 2 = only i <= j
     int herm;       // crt_tri_kernel, complex types (gemmul8_herk): the scalars are real (device scalars: ONE real each), and on row == col the incoming
                     // imaginary part counts as 0 and +0.0 is stored
+    void* const* pc;  // pointer-array batch (crt_kernel<..., PTR = true> only): non-null = item z's C is pc[z] (device memory; C and bc are not used).  Such an item is only
+                      // element-aligned as far as the host knows: every 16-byte form of crt_unit tests the address it actually stores to
 };
+// C of item blockIdx.z of a batched launch (register forms).  PTR = true: crt_kernel<..., true> only, the instantiation a pointer-array batch runs -- a pointer loaded
+// from memory is a generic one to the compiler, and in one expression with it the accesses to C would be flat ones in every kernel
+template <bool PTR> __device__ __forceinline__ char* crt_item_c(const CrtArgs& a) {
+    if constexpr (PTR) return a.pc ? (char*)a.pc[blockIdx.z] : (char*)a.C + blockIdx.z * a.bc;
+    else return (char*)a.C + blockIdx.z * a.bc;
+}
 
 // host side (oz2_crt.hip)
 void fill_crt_tables(CrtArgs& a, int dtype, int backend, unsigned N);

@@ -294,23 +294,26 @@ static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int 
     const int force1 = knobs().bounds_one_read;
     // (by default only 16-byte aligned operands: its loads are pipelined where every 16-byte row group is aligned, an unaligned operand walks tile by tile)
     const size_t esz = is_f32(dtype) ? 4 : 8;
-    auto one_read = [&](bool run, bool kmaj, size_t rows, const void* X, size_t ld) {
+    auto one_read = [&](bool run, bool kmaj, size_t rows, const void* X, size_t ld, const void* const* xp) {
+        if (xp) return false;  // a pointer-array operand: its address (the alignment below) is not the host's to read, and the panel kernel is a single-GEMM form
         const bool aligned = ((reinterpret_cast<uintptr_t>(X) | (ld * esz)) & 15u) == 0;
         if (sym) return false;  // a symmetric-form operand keeps the two-pass form, and its partner shares its launches
         return run && !kmaj && extract_one_read_ok(dtype, backend, L->kp) && (force1 < 0 ? rows >= kOneReadMinRows && aligned : force1 == 1);
     };
-    const bool orA = one_read(runA, kmajA, m, A, lda), orB = one_read(runB, kmajB, n, B, ldb);
+    const bool orA = one_read(runA, kmajA, m, A, lda, g_batch.pa), orB = one_read(runB, kmajB, n, B, ldb, g_batch.pb);
     const size_t srA = runA && !kmajA && !orA ? L->mp : 0, srB = runB && !kmajB && !orB ? np : 0;  // padded row counts of the operands that need the pass
     const size_t room = (L->scratch_bytes - scale_fixed_bytes(L->mp, np)) / ub;
     ExtractOperand ea, eb;
     if (runA) {
         ea = ExtractOperand{kmajA, conjA, m, A, lda, (int8_t*)L->A_bound, bstrideA, L->sftA, s0A, g_batch.sa, nullptr, 1, L->mp};
         ea.one_read = orA;
+        ea.xptr = g_batch.pa;
         if (srA) ea.amax = amax, ea.parts = amax_parts_for(m, k, room * srA / (srA + srB) / srA);
     }
     if (runB) {
         eb = ExtractOperand{kmajB, conjB, n, B, ldb, (int8_t*)L->B_bound, bstrideB, L->sftB, s0B, g_batch.sb, nullptr, 1, np};
         eb.one_read = orB;
+        eb.xptr = g_batch.pb;
         if (srB) eb.amax = (char*)amax + (srA ? (size_t)ea.parts * srA * ub : 0), eb.parts = amax_parts_for(n, k, room * srB / (srA + srB) / srB);
     }
     if (sym) (sym->onB ? eb : ea).sym = sym->form, (sym->onB ? eb : ea).herm = sym->herm;
@@ -328,6 +331,7 @@ static int scale_bounds_nf(void* stream_, int dtype, int backend, int op_A, int 
         FlagOperand fa, fb;
         if (runA) fa = FlagOperand{kmajA, m, A, lda, g_batch.sa, L->sftA, s0A, (int8_t*)L->A_bound, L->kp, L->parts, bstrideA};
         if (runB) fb = FlagOperand{kmajB, n, B, ldb, g_batch.sb, L->sftB, s0B, (int8_t*)L->B_bound, L->kp, L->parts, bstrideB};
+        fa.xptr = g_batch.pa, fb.xptr = g_batch.pb;
         OZ2_HIP(launch_flag_pair(stream, dtype, k, fa, fb));
     }
     if (col_end > col_begin) {
@@ -384,6 +388,7 @@ static int scale_finish_nf(void* stream_, int dtype, int backend, int op_A, int 
     if (!skipA) oa = QuantOperand{kmajA, conjA, m, A, lda, L->sftA, (int8_t*)L->A_lo, L->sizeA, L->part_strideA, g_batch.sa, f6 ? L->mp : 0};
     if (!skipB) ob = QuantOperand{kmajB, conjB, n, B, ldb, L->sftB, (int8_t*)L->B_lo, L->sizeB, L->part_strideB, g_batch.sb, f6 ? n : 0};
     oa.nf = ob.nf = nf;
+    oa.xptr = g_batch.pa, ob.xptr = g_batch.pb;
     if (twinA) oa.lo2 = twinA->lo, oa.plane_stride2 = twinA->plane_stride, oa.part_stride2 = twinA->part_stride;
     if (sym) (sym->onB ? ob : oa).sym = sym->form, (sym->onB ? ob : oa).herm = sym->herm;
     if (sym && sym->conj) (sym->onB ? ob : oa).conj = cplx;
@@ -393,6 +398,7 @@ static int scale_finish_nf(void* stream_, int dtype, int backend, int op_A, int 
             FlagOperand fa, fb;
             if (!skipA) fa = FlagOperand{kmajA, m, A, lda, g_batch.sa, L->sftA};
             if (!skipB) fb = FlagOperand{kmajB, n, B, ldb, g_batch.sb, L->sftB};
+            fa.xptr = g_batch.pa, fb.xptr = g_batch.pb;
             OZ2_HIP(launch_flag_pair(stream, dtype, k, fa, fb));
         }
     } else {
@@ -1208,9 +1214,11 @@ size_t gemmul8_work_size_batched(int is_complex, int backend, size_t m, size_t n
     return gemmul8_batched_item_bytes(is_complex, backend, m, n, k, N) * batch + 256;
 }
 
-int gemmul8_gemm_batched(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* alpha,
-                         const void* A, size_t lda, long long strideA, const void* B, size_t ldb, long long strideB, const void* beta,
-                         void* C, size_t ldc, long long strideC, size_t batch, unsigned N, int fastmode, void* work) {
+// the body of both batched entry points.  Strided form (ptr == false): A, B, C and the strides.  Pointer-array form: the three device arrays pa, pb, pc.
+static int gemm_batched_impl(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* alpha, const void* A, size_t lda,
+                             long long strideA, const void* B, size_t ldb, long long strideB, const void* beta, void* C, size_t ldc, long long strideC,
+                             bool ptr, const void* const* pa, const void* const* pb, void* const* pc, size_t batch, unsigned N, int fastmode, void* work) {
+    if (ptr) A = pa, B = pb, C = (void*)pc;  // (one null check for both forms, in one place of the order of checks)
     if (dtype < 0 || dtype > 3 || backend < 0 || backend > 1) return GEMMUL8_E_ARG;
     if (!moduli_ok(dtype, N)) return GEMMUL8_E_NUM_MODULI;
     if (!alpha || !beta || !A || !B || !C || !work) return GEMMUL8_E_ARG;
@@ -1227,9 +1235,11 @@ int gemmul8_gemm_batched(void* stream_, int dtype, int backend, int op_A, int op
     const bool alpha_dev = nf && scalars_on_device(alpha);
     for (size_t b0 = 0; b0 < batch; b0 += 65535) {  // gridDim.z limit
         const size_t nb = std::min<size_t>(65535, batch - b0);
-        const char* Ab = (const char*)A + (long long)b0 * strideA * (long long)esz;
-        const char* Bb = (const char*)B + (long long)b0 * strideB * (long long)esz;
-        char* Cb = (char*)C + (long long)b0 * strideC * (long long)esz;
+        // a chunk advances the base address, or -- host arithmetic on the ARRAY's address only -- the pointer array itself; in pointer mode the "operand"
+        // handed down is the array (non-null, what the phase functions check), which no kernel uses as an operand address
+        const char* Ab = ptr ? (const char*)(pa + b0) : (const char*)A + (long long)b0 * strideA * (long long)esz;
+        const char* Bb = ptr ? (const char*)(pb + b0) : (const char*)B + (long long)b0 * strideB * (long long)esz;
+        char* Cb = ptr ? (char*)(pc + b0) : (char*)C + (long long)b0 * strideC * (long long)esz;
         char* wb = w0 + b0 * W;
         gemmul8_layout L;
         int rc = gemmul8_get_layout(dtype, backend, m, n, k, N, wb, nullptr, nullptr, 0, 0, &L);
@@ -1239,6 +1249,7 @@ int gemmul8_gemm_batched(void* stream_, int dtype, int backend, int op_A, int op
         g_batch.sa = (size_t)(strideA * (long long)esz);  // negative strides wrap: pointer arithmetic is modular
         g_batch.sb = (size_t)(strideB * (long long)esz);
         g_batch.sc = (size_t)(strideC * (long long)esz);
+        if (ptr) g_batch.pa = pa + b0, g_batch.pb = pb + b0, g_batch.pc = pc + b0;
         rc = scale_nf(stream_, dtype, backend, op_A, op_B, m, n, k, Ab, lda, Bb, ldb, N, fastmode, 0, N, &L, 0, 0, nf);
         if (rc) return rc;
         rc = gemmul8_lowprec_gemm(stream_, dtype, backend, m, n, k, N, 0, N, &L);
@@ -1249,6 +1260,24 @@ int gemmul8_gemm_batched(void* stream_, int dtype, int backend, int op_A, int op
             OZ2_HIP(launch_nonfinite_patch((hipStream_t)stream_, dtype, norm_op(op_A), norm_op(op_B), m, n, k, alpha, alpha_dev, Ab, lda, Bb, ldb, L.sftA, L.sftB, Cb, ldc));
     }
     return GEMMUL8_OK;
+}
+
+int gemmul8_gemm_batched(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* alpha,
+                         const void* A, size_t lda, long long strideA, const void* B, size_t ldb, long long strideB, const void* beta,
+                         void* C, size_t ldc, long long strideC, size_t batch, unsigned N, int fastmode, void* work) {
+    return gemm_batched_impl(stream_, dtype, backend, op_A, op_B, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, false, nullptr,
+                             nullptr, nullptr, batch, N, fastmode, work);
+}
+
+// ---- the same batch with the items' addresses in three DEVICE arrays (hipblas?gemmBatched in the hook).  The arrays are read by the kernels only, item
+// blockIdx.z its own entry, in stream order: no copy to the host, no synchronisation, capturable.  What the strided path decides on the host from an
+// operand address is decided per item in the kernels (the scaling kernels' 16-byte loads, the CRT's 16-byte stores) or not taken (CRT LDS-DMA form,
+// one-read bound extract): all of these are bit-identical alternatives.
+int gemmul8_gemm_batched_ptr(void* stream_, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k, const void* alpha,
+                             const void* const* A_array, size_t lda, const void* const* B_array, size_t ldb, const void* beta, void* const* C_array,
+                             size_t ldc, size_t batch, unsigned N, int fastmode, void* work) {
+    return gemm_batched_impl(stream_, dtype, backend, op_A, op_B, m, n, k, alpha, nullptr, lda, 0, nullptr, ldb, 0, beta, nullptr, ldc, 0, true, A_array,
+                             B_array, C_array, batch, N, fastmode, work);
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@
 //   hipblas{S,D,C,Z}gemm_64, hipblasGemmEx_64,                              yes (ROCm 7 ILP64 / WithFlags twins): the same contract; emulated when every
 //     hipblasGemmExWithFlags, hipblasGemmExWithFlags_64                       dimension fits an int, native otherwise
 //   hipblas{S,D,C,Z}gemmStridedBatched, hipblasGemmStridedBatchedEx         yes (torch.bmm): no early out, degenerate calls are the native routine's
+//   hipblas{S,D,C,Z}gemmBatched(_64), hipblasGemmBatchedEx(_64),            yes (pointer arrays in device memory): one set of launches through gemmul8_gemm_batched_ptr, the
+//     hipblasGemmBatchedExWithFlags(_64)                                      arrays are never read on the host; no per-item fallback, see emulate_batch_ptr
 //   hipblas{S,D,C,Z}syrk(_64), hipblas{C,Z}herk(_64)                        yes: one triangle through gemmul8_syrk / gemmul8_herk (INT8 backend, k <= 2^17; HERK: real
 //                                                                             alpha / beta, N / C only); everything else is the native routine's, see try_syrk_impl
 //   hipblas{S,D,C,Z}syr2k(_64)                                              yes: one triangle through gemmul8_syr2k (INT8 backend, k <= 2^16, N / T only); see try_syrk_impl
@@ -24,6 +26,7 @@
 //   hipblasLtMatrixLayoutCreate / SetAttribute / Destroy                    yes: record what a layout holds (hipBLASLt cannot be asked)
 //   rocblas_{s,d,c,z}gemm, rocblas_{s,d,c,z}gemm_strided_batched,           yes, only with GEMMUL8_HOOK_ROCBLAS=1: applications that call rocBLAS directly
 //     rocblas_gemm_ex (in-place form), rocblas_destroy_handle                 (HPL-style codes)
+//   rocblas_{s,d,c,z}gemm_batched(_64), rocblas_gemm_batched_ex (in place)  yes, only with GEMMUL8_HOOK_ROCBLAS=1: the pointer-array forms, as for hipBLAS
 //   rocblas_internal_gemm_template<T> / _64<T>, T = float, double,          yes, only with GEMMUL8_HOOK_ROCBLAS=1 and a tested rocBLAS release: rocSOLVER's
 //     rocblas_complex_num<float / double> (eight mangled names)               trailing updates (INTEGRATION.md "What the hook reaches")
 //   gemmul8_hook_would_emulate, gemmul8_hook_rocblas_version_tested         this project's own queries (no interposition)
@@ -44,6 +47,8 @@
 //   GEMMUL8_DIST                   per call    blocks | moduli | fp64sum: shard every emulated GEMM over the ranks of an SPMD job (try_dist)
 //   GEMMUL8_BATCH_FUSED, GEMMUL8_BATCH_WORKSPACE_MB, GEMMUL8_BATCH_STREAMS
 //                                  per call    strided batches: one set of launches (default) in chunks of the given size, or lanes (emulate_batch)
+//                                              pointer-array batches: one set of launches in chunks of the given size; GEMMUL8_BATCH_FUSED=0 (or GEMMUL8_DIST)
+//                                              = the native routine, said once (emulate_batch_ptr: the lanes would walk item addresses on the host)
 //   GEMMUL8_HOOK_ROCBLAS           per call    "1" = the rocBLAS entry points above act
 //   GEMMUL8_ROCBLAS_ABI_UNCHECKED  once        "1" = interpose the internal template on any rocBLAS release (rocblas_internal_abi_ok)
 //   GEMMUL8_HOOK_STATS             once        "1" = print at exit how many GEMM calls / flops were emulated and how many went native (count_call);
@@ -75,14 +80,15 @@
 
 // The C ABI the hook calls: X(name, attribute) for gemmul8_<name>.  Everything that concerns these symbols is generated from this list.
 // `weak` marks an entry a library linked with this file may lack (tests/sanitize/mock_gpu.cpp has no gemmul8_set_nonfinite_mode: the mode
-// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_her2k / gemmul8_symm / gemmul8_hemm / gemmul8_trmm / gemmul8_trsm: every such call then goes to the native routine); the shim, which binds to this
+// then stays 0 -- and no gemmul8_syrk / gemmul8_herk / gemmul8_syr2k / gemmul8_her2k / gemmul8_symm / gemmul8_hemm / gemmul8_trmm / gemmul8_trsm / gemmul8_gemm_batched_ptr: every such call then goes to the native routine); the shim, which binds to this
 // project's own libgemmul8.so, requires every entry.
 #define OZ2_ABI(X)                                                                                          \
     X(work_size, ) X(gemm, ) X(work_size_batched, ) X(gemm_batched, ) X(add_row_bias, ) X(set_fp8_bound_mode, ) \
     X(comm_rccl_from_env, ) X(dist_create, ) X(dist_gemm, ) X(dist_allgather_c, ) X(dist_destroy, )             \
     X(set_nonfinite_mode, __attribute__((weak))) X(syrk, __attribute__((weak))) X(herk, __attribute__((weak))) \
     X(syr2k, __attribute__((weak))) X(symm, __attribute__((weak))) X(hemm, __attribute__((weak))) X(her2k, __attribute__((weak))) \
-    X(trmm, __attribute__((weak))) X(trsm, __attribute__((weak))) X(trsm_work_size, __attribute__((weak)))
+    X(trmm, __attribute__((weak))) X(trsm, __attribute__((weak))) X(trsm_work_size, __attribute__((weak))) \
+    X(gemm_batched_ptr, __attribute__((weak)))
 #ifndef OZ2_HOOK_SHIM
 #define X(name, attr) extern "C" attr decltype(::gemmul8_##name) gemmul8_##name;
 OZ2_ABI(X)
@@ -1281,6 +1287,74 @@ bool emulate_batch(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* s
     return true;
 }
 
+// Pointer-array batches (hipblas?gemmBatched, hipblasGemmBatchedEx, rocblas_?gemm_batched; not hooked by the reference): c.A / c.B / c.C are the three
+// DEVICE arrays of item addresses, c.sa / c.sb / c.sc are unused.  The hook never reads an array: the only path is the fused one (gemmul8_gemm_batched_ptr:
+// the kernels load their item's entries in stream order; capturable), for every batch >= 1.  The stream-lane and serial forms of emulate_batch walk item
+// addresses on the host and do not exist here: what they would take goes to the native routine, said once.  GEMMUL8_BATCH_WORKSPACE_MB chunks the batch as
+// for the strided form, by offsetting the three arrays (host arithmetic on the arrays' own addresses).  The `auto` floor is the strided batches' model.
+// GEMMUL8_HOOK_STATS: every call that arrives here is counted once, emulated or native, as try_emulate counts single GEMMs.
+bool emulate_batch_ptr(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* status, const hipStream_t* explicit_stream = nullptr) {
+    *status = HIPBLAS_STATUS_SUCCESS;
+    if (tl_native_depth > 0) return false;  // see try_emulate
+    enum { kNoFused, kDist, kNoSymbol, kNoWorkspace, kModuli, kKRange, kDeclined, kReasons };
+    auto native = [&](int why, long long detail = 0) {
+        static std::once_flag told[kReasons];
+        static const char* const text[kReasons] = {
+            "GEMMUL8_BATCH_FUSED=0: only the fused path can serve a pointer-array batch (the arrays are not read on the host)",
+            "GEMMUL8_DIST is set: the multi-GPU plans do not take pointer-array batches",
+            "the library has no gemmul8_gemm_batched_ptr",
+            "the workspace of the first chunk could not be allocated",
+            "the moduli count of GEMMUL8_NUM_MOD_{S,D,C,Z} is outside the type's range",
+            "k is beyond the emulator's range",
+            "the emulator declined the call",
+        };
+        std::call_once(told[why], [&] {
+            char num[32] = "";
+            if (detail) std::snprintf(num, sizeof num, " (%lld)", detail);
+            std::fprintf(stderr, "[GEMMUL8 HOOK] pointer-array batched %cGEMM %d x %d x %d (batch %d): %s%s -- using the native routine for such calls "
+                                 "(this message is printed once)\n", "SDCZ"[c.dtype], c.m, c.n, c.k, c.batch, text[why], num);
+        });
+        count_call(false, c);
+        return false;
+    };
+    const int dtype = c.dtype;
+    Selection s;
+    if (!selection_from_env(dtype, &s)) {
+        if (s.N != 0) return native(kModuli, (long long)s.N);  // asked for, but not a count the type has
+        return count_call(false, c), false;                     // the environment does not ask for this type: silent, as everywhere
+    }
+    if (!selected(c, &s, true)) return count_call(false, c), false;  // below the floor (logged once by below_floor)
+    if (env_u64("GEMMUL8_BATCH_FUSED", 1) == 0) return native(kNoFused);
+    if (dist_kind_from_env() >= 0) return native(kDist);
+    const auto fn = abi().gemm_batched_ptr;
+    if (!fn) return native(kNoSymbol);
+    if (!k_in_range(c, s)) return native(kKRange, c.k);
+    LockedState l = lock_ordered(handle, explicit_stream);
+    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
+    HandleState* const sp = l.sp.get();
+    hipStream_t stream = l.stream;
+    const size_t batch = (size_t)c.batch;
+    const size_t item = abi().work_size_batched(kTypes[dtype].cplx, s.backend, (size_t)c.m, (size_t)c.n, (size_t)c.k, s.N, 1) - 256;
+    const size_t budget = (size_t)env_u64("GEMMUL8_BATCH_WORKSPACE_MB", 4096) << 20;
+    const size_t per_chunk = std::max<size_t>(1, std::min<size_t>(batch, item ? budget / item : batch));
+    if (grow(sp->wC, item * per_chunk + 256, stream, "workC (pointer-array batch)") != HIPBLAS_STATUS_SUCCESS) {
+        (void)hipGetLastError();  // allocation failed: clear the sticky error
+        return native(kNoWorkspace, (long long)(item * per_chunk + 256));
+    }
+    sp->last.valid = false;  // the skip-scaling cache describes single calls; the planes are overwritten here
+    const void* const* pa = (const void* const*)c.A;
+    const void* const* pb = (const void* const*)c.B;
+    void* const* pc = (void* const*)c.C;
+    for (size_t b0 = 0; b0 < batch; b0 += per_chunk) {
+        const size_t nb = std::min(per_chunk, batch - b0);
+        const int rc = fn(stream, dtype, s.backend, (int)c.ta, (int)c.tb, (size_t)c.m, (size_t)c.n, (size_t)c.k, c.alpha, pa + b0, (size_t)c.lda, pb + b0,
+                          (size_t)c.ldb, c.beta, pc + b0, (size_t)c.ldc, nb, s.N, s.fast, sp->wC.ptr);
+        if (rc < 0 && b0 == 0) return native(kDeclined, rc);  // nothing written yet: the call is still the native routine's
+        if (rc != 0) return *status = HIPBLAS_STATUS_INTERNAL_ERROR, true;
+    }
+    return count_call(true, c), true;
+}
+
 
 // ---- rocBLAS entry points, opt-in with GEMMUL8_HOOK_ROCBLAS=1 (no counterpart in the reference: src/hook.cu:846-1055 hooks the cuBLAS / hipBLAS
 // names only).  For applications that call rocBLAS directly.  The handle of a hipBLAS call IS the rocBLAS handle, so a call the hipBLAS hooks
@@ -1481,6 +1555,15 @@ bool batched_gemm(hipblasHandle_t handle, int dtype, hipblasOperation_t ta, hipb
     GemmCall c;
     return gemm_call(&c, dtype, ta, tb, m, n, k, alpha, A, lda, sa, B, ldb, sb, beta, C, ldc, sc, batch) && alpha && beta && emulate_batch(handle, c, st);
 }
+// Pointer-array entry points: the same contract (no early out).  A, B, C are the device arrays of item addresses; they ride in the call record's
+// A / B / C with strides 0 and are only ever handed on (emulate_batch_ptr).
+bool batched_ptr_gemm(hipblasHandle_t handle, int dtype, int ta, int tb, int64_t m, int64_t n, int64_t k, const void* alpha, const void* A, int64_t lda,
+                      const void* B, int64_t ldb, const void* beta, const void* C, int64_t ldc, int64_t batch, hipblasStatus_t* st,
+                      const hipStream_t* explicit_stream = nullptr) {
+    GemmCall c;
+    return gemm_call(&c, dtype, ta, tb, m, n, k, alpha, A, lda, 0, B, ldb, 0, beta, const_cast<void*>(C), ldc, 0, batch) && alpha && beta &&
+           emulate_batch_ptr(handle, c, st, explicit_stream);
+}
 
 }  // namespace
 
@@ -1520,6 +1603,37 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
             return st;                                                                                                                  \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, transA, transB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB,      \
                    beta, C, ldc, strideC, batchCount);                                                                                  \
+    }
+#define OZ2_PB_HOOK(NAME, T, I, CODE)                                                                                                   \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, I m, I n, I k, const T* alpha,   \
+                         const T* const A[], I lda, const T* const B[], I ldb, const T* beta, T* const C[], I ldc, I batchCount) {      \
+        hipblasStatus_t st;                                                                                                             \
+        if (batched_ptr_gemm(handle, CODE, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, batchCount, &st)) return st;   \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, batchCount); \
+    }
+// hipblasGemmBatchedEx and its _64 / WithFlags twins: the type / compute combinations of the strided Ex hook (dtype_of)
+#define OZ2_PB_EX_HOOK(NAME, I, ...)                                                                                                    \
+    hipblasStatus_t NAME(hipblasHandle_t handle, hipblasOperation_t transA, hipblasOperation_t transB, I m, I n, I k, const void* alpha, \
+                         const void* A[], hipDataType aType, I lda, const void* B[], hipDataType bType, I ldb, const void* beta, void* C[], \
+                         hipDataType cType, I ldc, I batchCount, hipblasComputeType_t computeType,                                      \
+                         hipblasGemmAlgo_t algo __VA_OPT__(, hipblasGemmFlags_t) __VA_ARGS__) {                                         \
+        hipblasStatus_t st;                                                                                                             \
+        if (batched_ptr_gemm(handle, dtype_of(aType, bType, cType, computeType), transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, \
+                             batchCount, &st))                                                                                          \
+            return st;                                                                                                                  \
+        OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, transA, transB, m, n, k, alpha, A, aType, lda, B, bType, ldb, beta, C, \
+                   cType, ldc, batchCount, computeType, algo __VA_OPT__(, ) __VA_ARGS__);                                               \
+    }
+// rocblas_{s,d,c,z}gemm_batched and the _64 twin: act only with GEMMUL8_HOOK_ROCBLAS=1 (rocblas_takes)
+#define OZ2_ROCBLAS_PB_HOOK(NAME, T, I, CODE)                                                                                           \
+    int NAME(void* handle, int transA, int transB, I m, I n, I k, const T* alpha, const T* const A[], I lda, const T* const B[], I ldb, \
+             const T* beta, T* const C[], I ldc, I batchCount) {                                                                        \
+        hipStream_t s_;                                                                                                                 \
+        hipblasStatus_t st_;                                                                                                            \
+        if (tl_native_depth == 0 && rocblas_takes(handle, transA, transB, &s_) &&                                                       \
+            batched_ptr_gemm((hipblasHandle_t)handle, CODE, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, batchCount, &st_, &s_)) \
+            return rocblas_status_of(st_);                                                                                              \
+        OZ2_NATIVE(NAME, 6, handle, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, batchCount);                          \
     }
 // the trailing argument, if any, is the `flags` of the WithFlags forms
 #define OZ2_GEMM_EX_HOOK(NAME, I, ...)                                                                                                  \
@@ -1625,6 +1739,10 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     OZ2_GEMM_HOOK(hipblas##U##gemm, T, int, CODE)                                                                                       \
     OZ2_GEMM_HOOK(hipblas##U##gemm_64, T, int64_t, CODE)                                                                                \
     OZ2_SB_HOOK(hipblas##U##gemmStridedBatched, T, CODE)                                                                                \
+    OZ2_PB_HOOK(hipblas##U##gemmBatched, T, int, CODE)                                                                                  \
+    OZ2_PB_HOOK(hipblas##U##gemmBatched_64, T, int64_t, CODE)                                                                           \
+    OZ2_ROCBLAS_PB_HOOK(rocblas_##L##gemm_batched, T, int, CODE)                                                                        \
+    OZ2_ROCBLAS_PB_HOOK(rocblas_##L##gemm_batched_64, T, int64_t, CODE)                                                                 \
     OZ2_SYRK_HOOK(hipblas##U##syrk, T, int, CODE)                                                                                       \
     OZ2_SYRK_HOOK(hipblas##U##syrk_64, T, int64_t, CODE)                                                                                \
     OZ2_SYR2K_HOOK(hipblas##U##syr2k, T, int, CODE)                                                                                     \
@@ -1662,10 +1780,17 @@ OZ2_GEMM_EX_HOOK(hipblasGemmEx, int)
 OZ2_GEMM_EX_HOOK(hipblasGemmEx_64, int64_t)
 OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags, int, flags)
 OZ2_GEMM_EX_HOOK(hipblasGemmExWithFlags_64, int64_t, flags)
+OZ2_PB_EX_HOOK(hipblasGemmBatchedEx, int)
+OZ2_PB_EX_HOOK(hipblasGemmBatchedEx_64, int64_t)
+OZ2_PB_EX_HOOK(hipblasGemmBatchedExWithFlags, int, flags)
+OZ2_PB_EX_HOOK(hipblasGemmBatchedExWithFlags_64, int64_t, flags)
 #undef OZ2_TYPE_HOOKS
 #undef OZ2_ROCBLAS_INTERNAL
 #undef OZ2_ROCBLAS_HOOK
 #undef OZ2_GEMM_EX_HOOK
+#undef OZ2_ROCBLAS_PB_HOOK
+#undef OZ2_PB_EX_HOOK
+#undef OZ2_PB_HOOK
 #undef OZ2_HERK_HOOK
 #undef OZ2_HER2K_HOOK
 #undef OZ2_SYMM_HOOK
@@ -1707,6 +1832,20 @@ int rocblas_gemm_ex(void* handle, int transA, int transB, int m, int n, int k, c
         return rocblas_status_of(st_);
     OZ2_NATIVE(rocblas_gemm_ex, 6, handle, transA, transB, m, n, k, alpha, a, a_type, lda, b, b_type, ldb, beta, c, c_type, ldc, d, d_type, ldd, compute_type,
                algo, solution_index, flags);
+}
+
+// rocblas_gemm_batched_ex: the pointer-array twin of rocblas_gemm_ex, under the same conditions (one plain type, the in-place form c == d, ldc == ldd)
+int rocblas_gemm_batched_ex(void* handle, int transA, int transB, int m, int n, int k, const void* alpha, const void* a, int a_type, int lda,
+                            const void* b, int b_type, int ldb, const void* beta, const void* c, int c_type, int ldc, void* d, int d_type, int ldd,
+                            int batch_count, int compute_type, int algo, int32_t solution_index, uint32_t flags) {
+    const bool same = a_type == b_type && b_type == c_type && c_type == d_type && d_type == compute_type;
+    hipStream_t s_;
+    hipblasStatus_t st_;
+    if (same && c == d && ldc == ldd && tl_native_depth == 0 && rocblas_takes(handle, transA, transB, &s_) &&
+        batched_ptr_gemm((hipblasHandle_t)handle, dtype_of_rocblas(a_type), transA, transB, m, n, k, alpha, a, lda, b, ldb, beta, d, ldd, batch_count, &st_, &s_))
+        return rocblas_status_of(st_);
+    OZ2_NATIVE(rocblas_gemm_batched_ex, 6, handle, transA, transB, m, n, k, alpha, a, a_type, lda, b, b_type, ldb, beta, c, c_type, ldc, d, d_type, ldd,
+               batch_count, compute_type, algo, solution_index, flags);
 }
 
 hipblasStatus_t hipblasLtMatrixLayoutCreate(hipblasLtMatrixLayout_t* matLayout, hipDataType type, uint64_t rows, uint64_t cols, int64_t ld) {

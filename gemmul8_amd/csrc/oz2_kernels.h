@@ -29,6 +29,12 @@ struct BatchCtx {
     unsigned batch = 1;
     size_t ws = 0;                // bytes between the items' workspaces
     size_t sa = 0, sb = 0, sc = 0;  // bytes between the items' A, B, C
+    // pointer-array batch (gemmul8_gemm_batched_ptr): a non-null array holds the items' operand addresses in DEVICE memory and replaces base + b * stride
+    // for that operand.  Only kernels read the arrays (item blockIdx.z loads its own entry); the host never does, so nothing that the strided path decides
+    // on the host from an operand's address (16-byte forms, the one-read extract) may be decided for such an operand.  The entries are not validated.
+    const void* const* pa = nullptr;
+    const void* const* pb = nullptr;
+    void* const* pc = nullptr;
 };
 inline thread_local BatchCtx g_batch;
 
@@ -103,6 +109,7 @@ struct ExtractOperand {
     bool one_read = false;     // row-strided operand: row maxima and bound plane from one read (no amax_pair_kernel pass, `amax` unused); needs extract_one_read_ok
     int sym = kSymNone;        // symmetric form (SymForm); keeps the two-pass form (not one_read)
     bool herm = false;
+    const void* const* xptr = nullptr;  // pointer-array batch (BatchCtx::pa / pb): item z's operand is xptr[z], X and xstride are not used; never one_read
 };
 bool extract_one_read_ok(int dtype, int backend, size_t kp);  // the one-read form exists: real types, INT8 planes, a single GEMM, kp <= 8192
 unsigned amax_parts_for(size_t rows, size_t k, size_t max_parts);
@@ -134,6 +141,7 @@ struct QuantOperand {
     size_t plane_stride2 = 0, part_stride2 = 0;
     int sym = kSymNone;  // symmetric form (SymForm): the launches that carry such an operand are the *_sym_pair kernels of oz2_scale.hip
     bool herm = false;
+    const void* const* xptr = nullptr;  // pointer-array batch (BatchCtx::pa / pb): item z's operand is xptr[z], X and xstride are not used
 };
 // FP8 backend: the residue planes are FP6 panel images whenever B's last row block fits its share of the reference's plane size
 // (16-row granules at 3/4 byte per element: n >= 45; 64 keeps whole wave tiles); GEMMUL8_FP8_PLANES=e4m3 keeps the e4m3 byte planes
@@ -174,6 +182,7 @@ struct FlagOperand {
     int16_t* sft_keep = nullptr;  // ... and, accurate mode, their scratch copy
     int8_t* bound = nullptr;    // accurate mode: bound plane(s), zeroed for a flagged row before the bound GEMM
     size_t kp = 0, parts = 0, part_stride = 0;
+    const void* const* xptr = nullptr;  // pointer-array batch (BatchCtx::pa / pb): item z's operand is xptr[z], X and xstride are not used
 };
 // flags both operands in ONE launch: reads every element once; run after the shifts are written and before anything consumes them
 hipError_t launch_flag_pair(hipStream_t stream, int dtype, size_t k, const FlagOperand& A, const FlagOperand& B);

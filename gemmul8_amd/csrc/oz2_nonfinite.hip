@@ -57,6 +57,7 @@ struct FlagArgs {
     int8_t* bound;         // accurate mode: bound plane(s), [rows][kp] bytes; nullptr in fast mode
     size_t kp, parts, part_stride;
     unsigned blocks;
+    const void* const* xp;  // pointer-array batch: item z's operand is xp[z] (X and bx are not used)
 };
 
 constexpr unsigned kStridedRows = 32;  // row-strided operand: 32 rows x 8 k-lanes per workgroup
@@ -79,10 +80,14 @@ __device__ __forceinline__ void flag_rows(const FlagArgs& o, size_t r0, const un
     }
 }
 
-template <typename T> __device__ __forceinline__ void flag_body(const FlagArgs& o, unsigned bid, size_t bw) {
+// PTR (the *_ptr_* kernels of a pointer-array batch, instantiations of their own: a loaded pointer is a generic one to the compiler and would turn the
+// loads of every kernel into flat loads): item z's operand is o.xp[z] where the operand has an array
+template <typename T, bool PTR = false> __device__ __forceinline__ void flag_body(const FlagArgs& o, unsigned bid, size_t bw) {
     __shared__ unsigned fl[kStridedRows];
     const size_t zw = (size_t)blockIdx.z * bw;
     const T* X = (const T*)((const char*)o.X + (size_t)blockIdx.z * o.bx);
+    if constexpr (PTR)
+        if (o.xp) X = (const T*)o.xp[blockIdx.z];
     if (o.kmajor) {  // one workgroup per row, lanes along k
         const size_t r = bid;
         const T* x = X + r * o.ld;
@@ -124,6 +129,10 @@ template <typename T> __global__ void __launch_bounds__(256) flag_pair_kernel(co
     if (blockIdx.x < a.blocks) flag_body<T>(a, blockIdx.x, bw);
     else flag_body<T>(b, blockIdx.x - a.blocks, bw);
 }
+template <typename T> __global__ void __launch_bounds__(256) flag_ptr_pair_kernel(const FlagArgs a, const FlagArgs b, size_t bw) {
+    if (blockIdx.x < a.blocks) flag_body<T, true>(a, blockIdx.x, bw);
+    else flag_body<T, true>(b, blockIdx.x - a.blocks, bw);
+}
 
 // ------------------------------------------------------------------ patch launch
 // Workgroups [0, nR): flagged rows of op(A); group (rg, cc) takes rows [256 rg, 256 rg + 256) and the 64 columns of chunk cc.
@@ -143,9 +152,13 @@ struct PatchArgs {
     const void* alpha_dev;  // device-resident alpha (nullptr: the host value above)
     unsigned chunksN, chunksM, nR;
     size_t sa, sb, sc, bw;  // batched launch: bytes between the items' A, B, C, workspaces
+    const void* const* pa;  // pointer-array batch (BatchCtx): a non-null array replaces base + z * stride for its operand
+    const void* const* pb;
+    void* const* pc;
 };
 
-template <typename T> __global__ void __launch_bounds__(256) nonfinite_patch_kernel(const PatchArgs p) {
+// PTR = true: the instantiation of a pointer-array batch (a template parameter: see flag_body)
+template <typename T, bool PTR = false> __global__ void __launch_bounds__(256) nonfinite_patch_kernel(const PatchArgs p) {
     using E = NF<T>;
     using U = typename E::U;
     __shared__ unsigned list[256];
@@ -164,6 +177,11 @@ template <typename T> __global__ void __launch_bounds__(256) nonfinite_patch_ker
     const T* A = (const T*)((const char*)p.A + (size_t)blockIdx.z * p.sa);
     const T* B = (const T*)((const char*)p.B + (size_t)blockIdx.z * p.sb);
     U* C = (U*)((char*)p.C + (size_t)blockIdx.z * p.sc);
+    if constexpr (PTR) {  // a pointer-array batch: the arrays replace base + z * stride, each on its own
+        if (p.pa) A = (const T*)p.pa[blockIdx.z];
+        if (p.pb) B = (const T*)p.pb[blockIdx.z];
+        if (p.pc) C = (U*)p.pc[blockIdx.z];
+    }
     const bool rowpart = blockIdx.x < p.nR;
     const unsigned bid = rowpart ? blockIdx.x : blockIdx.x - p.nR;
     const unsigned grp = bid / (rowpart ? p.chunksN : p.chunksM), chunk = bid - grp * (rowpart ? p.chunksN : p.chunksM);
@@ -223,13 +241,14 @@ template <typename T> hipError_t launch_flag_pair_t(hipStream_t stream, size_t k
     auto mk = [k](const FlagOperand& o) {
         FlagArgs f{};
         if (!o.rows) return f;
-        f = FlagArgs{o.X, o.ld, o.rows, k, o.xstride, o.kmajor ? 1 : 0, o.sft, o.sft_keep, o.bound, o.kp, o.parts, o.part_stride, 0u};
+        f = FlagArgs{o.X, o.ld, o.rows, k, o.xstride, o.kmajor ? 1 : 0, o.sft, o.sft_keep, o.bound, o.kp, o.parts, o.part_stride, 0u, o.xptr};
         f.blocks = (unsigned)(o.kmajor ? o.rows : (o.rows + kStridedRows - 1) / kStridedRows);
         return f;
     };
     const FlagArgs a = mk(A), b = mk(B);
     if (a.blocks + b.blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(flag_pair_kernel<T>, dim3(a.blocks + b.blocks, 1, g_batch.batch), dim3(256), 0, stream, a, b, g_batch.ws);
+    if (a.xp || b.xp) hipLaunchKernelGGL(flag_ptr_pair_kernel<T>, dim3(a.blocks + b.blocks, 1, g_batch.batch), dim3(256), 0, stream, a, b, g_batch.ws);
+    else hipLaunchKernelGGL(flag_pair_kernel<T>, dim3(a.blocks + b.blocks, 1, g_batch.batch), dim3(256), 0, stream, a, b, g_batch.ws);
     return hipGetLastError();
 }
 
@@ -270,12 +289,20 @@ hipError_t launch_nonfinite_patch(hipStream_t stream, int dtype, int opA, int op
     if (nR + nC > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     p.nR = (unsigned)nR;
     p.sa = g_batch.sa, p.sb = g_batch.sb, p.sc = g_batch.sc, p.bw = g_batch.ws;
+    p.pa = g_batch.pa, p.pb = g_batch.pb, p.pc = g_batch.pc;
     const dim3 grid((unsigned)(nR + nC), 1, g_batch.batch);
+    const bool ptr = p.pa || p.pb || p.pc;
+#define OZ2_PATCH(T)                                                                                       \
+    do {                                                                                                   \
+        if (ptr) hipLaunchKernelGGL((nonfinite_patch_kernel<T, true>), grid, dim3(256), 0, stream, p);     \
+        else hipLaunchKernelGGL((nonfinite_patch_kernel<T, false>), grid, dim3(256), 0, stream, p);        \
+    } while (0)
     switch (dtype) {
-    case kF32: hipLaunchKernelGGL(nonfinite_patch_kernel<float>, grid, dim3(256), 0, stream, p); break;
-    case kF64: hipLaunchKernelGGL(nonfinite_patch_kernel<double>, grid, dim3(256), 0, stream, p); break;
-    case kC32: hipLaunchKernelGGL(nonfinite_patch_kernel<float2>, grid, dim3(256), 0, stream, p); break;
-    case kC64: hipLaunchKernelGGL(nonfinite_patch_kernel<double2>, grid, dim3(256), 0, stream, p); break;
+    case kF32: OZ2_PATCH(float); break;
+    case kF64: OZ2_PATCH(double); break;
+    case kC32: OZ2_PATCH(float2); break;
+    case kC64: OZ2_PATCH(double2); break;
+#undef OZ2_PATCH
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -168,12 +168,24 @@ struct StageArgs {
     const void* X2;
     size_t ld2;
     size_t pitch;
+    // pointer-array batch (gemmul8_gemm_batched_ptr; read by the *_ptr_* kernels only): non-null = item z's operand is xp[z] (device memory; X and bx are
+    // not used).  Last, so that no other field moves.
+    const void* const* xp;
 };
 // item blockIdx.z of a batched launch: every workspace pointer moves by bw, the operand by bx (both 0 for a single GEMM).  The offsets
 // are applied at the few points of use: a modified COPY of the argument block lands in scratch memory (the quantise kernels ran 6x
 // slower that way).
 #define OZ2_ZW ((size_t)blockIdx.z * a.bw)
 #define OZ2_ZX ((size_t)blockIdx.z * a.bx)
+// The operand of item blockIdx.z.  PTR = false (every kernel but the *_ptr_* ones): X + z * bx, the only form those kernels hold.  PTR = true (the kernels of a
+// pointer-array batch, instantiations of their own): from the pointer array when the operand has one (one wave-uniform load), else the strided rule.  A pointer
+// loaded from memory is a generic one to the compiler, and merged into one expression with it the operand loads become flat loads: hence the instantiations.
+// Item pointers are not validated.  OZ2_XB is used inside templates that have a `PTR` parameter.
+template <bool PTR> __device__ __forceinline__ const char* item_base(const void* X, const void* const* xp, size_t bx) {
+    if constexpr (PTR) return xp ? (const char*)xp[blockIdx.z] : (const char*)X + (size_t)blockIdx.z * bx;
+    else return (const char*)X + (size_t)blockIdx.z * bx;
+}
+#define OZ2_XB(a_) item_base<PTR>((a_).X, (a_).xp, (a_).bx)
 __device__ __forceinline__ int fused_final_shift(const StageArgs& a, size_t row, bool writer, size_t zw) {
     const int s0 = ((const int16_t*)((const char*)a.fin_sft0 + zw))[row];
     if (a.nf && s0 == kNonfiniteSft) {  // flagged row (non-finite mode 1): the sentinel stays
@@ -557,7 +569,7 @@ __device__ __forceinline__ void emit4(const StageArgs& a, size_t row, size_t k0,
 }
 
 // K-major operand: one 256-thread block per row; thread = 4 consecutive k per 1024-wide sweep
-template <typename T, int MODE, bool TWIN = false>
+template <typename T, int MODE, bool TWIN = false, bool PTR = false>
 __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsigned bid) {
     using E = ET<T>;
     using U = typename E::U;
@@ -571,7 +583,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
             const size_t row = (size_t)rg * 8 + (threadIdx.x >> 5);
             const size_t k0 = (size_t)(bid - rg * nks) * 128 + (size_t)(threadIdx.x & 31) * 4;
             if (row >= a.rows) return;  // (uniform over the 32 lanes of a row)
-            const T* x = (const T*)((const char*)a.X + OZ2_ZX) + row * a.ld;
+            const T* x = (const T*)OZ2_XB(a) + row * a.ld;
             const int s = OZ2_ROW_SHIFT(a, row, bid == rg * nks && (threadIdx.x & 31) == 0);
             T v[4];
             load4<T>(x, k0, a.k, v);
@@ -586,7 +598,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
         const size_t row = bid / nch;
         const size_t k0 = (size_t)(bid - row * nch) * 1024 + (size_t)threadIdx.x * 4;
         if (k0 >= a.kp) return;
-        const T* x = (const T*)((const char*)a.X + OZ2_ZX) + row * a.ld;
+        const T* x = (const T*)OZ2_XB(a) + row * a.ld;
         const int s = OZ2_ROW_SHIFT(a, row, k0 == 0);
         T v[4];
         load4<T>(x, k0, a.k, v);
@@ -594,7 +606,7 @@ __device__ __forceinline__ void stage_kmajor_body(const StageArgs& a, const unsi
         return;
     }
     const size_t row = bid;
-    const T* x = (const T*)((const char*)a.X + OZ2_ZX) + row * a.ld;
+    const T* x = (const T*)OZ2_XB(a) + row * a.ld;
     int s;
     if constexpr (MODE == MODE_BOUND) {
         __shared__ U sm[4];
@@ -751,7 +763,7 @@ template <typename T> struct StageTile {
     static constexpr int TK = 128;
 };
 // SEG2 (the syr2k kernels): twice the k tiles, those of X first, then those of X2; the row maxima (MODE_BOUND) are those of both matrices' partial arrays
-template <typename T, int MODE, bool TWIN = false, bool SEG2 = false>
+template <typename T, int MODE, bool TWIN = false, bool SEG2 = false, bool PTR = false>
 __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const unsigned bid) {
     using E = ET<T>;
     using U = typename E::U;
@@ -802,7 +814,7 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
         constexpr int KY = 256 / RP;     // k values fetched per pass
         const int rp = threadIdx.x % RP, ky = threadIdx.x / RP;
         const size_t row = r0 + RPL * rp;
-        const T* x = (const T*)((const char*)Xs + OZ2_ZX) + row;
+        const T* x = (const T*)(SEG2 ? (const char*)Xs + OZ2_ZX : OZ2_XB(a)) + row;
         const bool pair_ok = row + RPL - 1 < a.rows && ((reinterpret_cast<uintptr_t>(x) | (ld * sizeof(T))) & 15u) == 0;
         typedef unsigned V4 __attribute__((ext_vector_type(4)));
         V4 buf[TK / KY];
@@ -833,7 +845,7 @@ __device__ __forceinline__ void stage_strided_body(const StageArgs& a, const uns
         constexpr int KY = 256 / TR;  // k values fetched per pass
         const int rx = threadIdx.x % TR, ky = threadIdx.x / TR;
         const size_t row = r0 + rx;
-        const T* x = (const T*)((const char*)Xs + OZ2_ZX) + row;
+        const T* x = (const T*)(SEG2 ? (const char*)Xs + OZ2_ZX : OZ2_XB(a)) + row;
 #pragma unroll 4
         for (int it = 0; it < TK / KY; ++it) {
             const int kk = ky + KY * it;
@@ -1054,6 +1066,20 @@ template <typename T> __global__ void __launch_bounds__(256) extract_pair_kernel
         else stage_strided_body<T, MODE_BOUND>(b, blockIdx.x - nA);
     }
 }
+// the same for a pointer-array batch (gemmul8_gemm_batched_ptr): instantiations of the bodies that take an item's operand from StageArgs::xp
+template <typename T> __global__ void __launch_bounds__(256) extract_ptr_pair_kernel(const StageArgs a, const StageArgs b, const unsigned nA, const int kmA, const int kmB) {
+    if (a.zero_words) {
+        unsigned* zp = (unsigned*)((char*)a.zero_p + OZ2_ZW);
+        for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < a.zero_words; i += gridDim.x * 256u) zp[i] = 0u;
+    }
+    if (blockIdx.x < nA) {
+        if (kmA) stage_kmajor_body<T, MODE_BOUND, false, true>(a, blockIdx.x);
+        else stage_strided_body<T, MODE_BOUND, false, false, true>(a, blockIdx.x);
+    } else {
+        if (kmB) stage_kmajor_body<T, MODE_BOUND, false, true>(b, blockIdx.x - nA);
+        else stage_strided_body<T, MODE_BOUND, false, false, true>(b, blockIdx.x - nA);
+    }
+}
 // The same launch when an operand takes the one-read form (real types).  Operand form (fA / fB): 0 = row-strided after amax_pair_kernel, 1 = K-major,
 // 2 = row-strided from one read (stage_panel_body).  A kernel of its own: the panel body's registers (4 instead of 5 workgroups per CU) would otherwise be
 // paid by every call of extract_pair_kernel, also where no operand takes the form (1024^3, launch-bound: +0.9 us measured with one kernel for both).
@@ -1082,6 +1108,16 @@ template <typename T> __global__ void __launch_bounds__(256) quantise_pair_kerne
     } else {
         if (kmB) stage_kmajor_body<T, MODE_MOD>(b, blockIdx.x - nA);
         else stage_strided_body<T, MODE_MOD>(b, blockIdx.x - nA);
+    }
+}
+// the same for a pointer-array batch
+template <typename T> __global__ void __launch_bounds__(256) quantise_ptr_pair_kernel(const StageArgs a, const StageArgs b, const unsigned nA, const int kmA, const int kmB) {
+    if (blockIdx.x < nA) {
+        if (kmA) stage_kmajor_body<T, MODE_MOD, false, true>(a, blockIdx.x);
+        else stage_strided_body<T, MODE_MOD, false, false, true>(a, blockIdx.x);
+    } else {
+        if (kmB) stage_kmajor_body<T, MODE_MOD, false, true>(b, blockIdx.x - nA);
+        else stage_strided_body<T, MODE_MOD, false, false, true>(b, blockIdx.x - nA);
     }
 }
 // gemmul8_herk: ONE complex operand, whose every loaded element leaves as five plane sets -- Re, Im, Re + Im at a.lo as above, and the conjugate
@@ -1123,7 +1159,7 @@ typedef unsigned v6u __attribute__((ext_vector_type(6)));
 // (Complex operands take the generic stage kernels, four k per lane.  A complex form of this kernel was built in round 5 -- the fragment in two halves of 16 k,
 // three plane sets per value -- and needs 282-314 registers: the 16-float operand tuples of the pack instruction with half their lanes as padding fragment
 // the register file; one wave per SIMD: not kept.)
-template <typename T> __device__ __forceinline__ void stage_f6_body(const StageArgs& a, const unsigned bid, const bool kmajor, char* tile /* this wave's 64 x 144 bytes */) {
+template <typename T, bool PTR = false> __device__ __forceinline__ void stage_f6_body(const StageArgs& a, const unsigned bid, const bool kmajor, char* tile /* this wave's 64 x 144 bytes */) {
     static_assert(!ET<T>::cplx, "real operands");
     constexpr int EPL = 16 / (int)sizeof(T);   // elements per 16-byte piece
     constexpr int CH = 128 / (int)sizeof(T);   // elements per 128-byte chunk of a row
@@ -1133,7 +1169,7 @@ template <typename T> __device__ __forceinline__ void stage_f6_body(const StageA
     if (kmajor) rb = bid / nks, kt = bid - rb * nks;   // the workgroups in flight walk along the rows' memory
     else kt = bid / nrb, rb = bid - kt * nrb;           // ... down the columns'
     const size_t r0 = (size_t)rb * 64, row = r0 + lane, k0 = (size_t)kt * 128 + (size_t)q * 32;
-    const T* X = (const T*)((const char*)a.X + OZ2_ZX);
+    const T* X = (const T*)OZ2_XB(a);
     typedef unsigned V4 __attribute__((ext_vector_type(4)));
     T v[32];
     if (kmajor) {
@@ -1297,6 +1333,13 @@ template <typename T> __global__ void __launch_bounds__(256) quantise_f6_pair_ke
     if (blockIdx.x < nA) stage_f6_body<T>(a, blockIdx.x, kmA != 0, mine);
     else stage_f6_body<T>(b, blockIdx.x - nA, kmB != 0, mine);
 }
+// the same for a pointer-array batch
+template <typename T> __global__ void __launch_bounds__(256) quantise_f6_ptr_pair_kernel(const StageArgs a, const StageArgs b, const unsigned nA, const int kmA, const int kmB) {
+    __shared__ __attribute__((aligned(16))) char tile[4][64 * 144];
+    char* const mine = tile[threadIdx.x >> 6];
+    if (blockIdx.x < nA) stage_f6_body<T, true>(a, blockIdx.x, kmA != 0, mine);
+    else stage_f6_body<T, true>(b, blockIdx.x - nA, kmB != 0, mine);
+}
 
 // per-row amax of row-strided operands, BOTH operands in one launch (round 6): workgroup = 64 rows x one of `parts` k splits, 256 threads = 64 rows x 4 k-lanes;
 // the maxima of split y go to the partial array y (amax + y * pstride): no atomics, nothing to zero; the extract takes the maximum over the splits.
@@ -1307,8 +1350,14 @@ struct AmaxOperand {
     size_t pstride;
     unsigned parts, row_groups;
 };
-template <typename T> __device__ __forceinline__ void amax_strided_body(const AmaxOperand& o, const unsigned bid, size_t k, size_t bw) {
-    const T* X = (const T*)((const char*)o.X + blockIdx.z * o.bx);  // batched launch: item blockIdx.z
+// the operand of amax_ptr_pair_kernel (a pointer-array batch): non-null xp = item z's operand is xp[z].  A type of its own: AmaxOperand keeps its layout.
+struct AmaxPtrOperand : AmaxOperand {
+    const void* const* xp;
+};
+template <typename T, typename O = AmaxOperand> __device__ __forceinline__ void amax_strided_body(const O& o, const unsigned bid, size_t k, size_t bw) {
+    const T* X;  // batched launch: item blockIdx.z
+    if constexpr (std::is_same<O, AmaxPtrOperand>::value) X = (const T*)item_base<true>(o.X, o.xp, o.bx);
+    else X = (const T*)((const char*)o.X + blockIdx.z * o.bx);
     using E = ET<T>;
     using U = typename E::U;
     using UB = typename std::conditional<sizeof(U) == 8, unsigned long long, unsigned>::type;
@@ -1382,6 +1431,11 @@ template <typename T> __global__ void __launch_bounds__(256) amax_pair_kernel(co
     if (blockIdx.x < nA) amax_strided_body<T>(a, blockIdx.x, k, bw);
     else amax_strided_body<T>(b, blockIdx.x - nA, k, bw);
 }
+// the same for a pointer-array batch
+template <typename T> __global__ void __launch_bounds__(256) amax_ptr_pair_kernel(const AmaxPtrOperand a, const AmaxPtrOperand b, const unsigned nA, size_t k, size_t bw) {
+    if (blockIdx.x < nA) amax_strided_body<T, AmaxPtrOperand>(a, blockIdx.x, k, bw);
+    else amax_strided_body<T, AmaxPtrOperand>(b, blockIdx.x - nA, k, bw);
+}
 
 template <typename T, int MODE> static size_t stage_blocks(bool kmajor, const StageArgs& a) {
     if (a.rows == 0) return 0;
@@ -1395,14 +1449,16 @@ template <typename T> static hipError_t launch_quantise_stage(hipStream_t stream
         if ((a.rows == 0 || a.f6) && (b.rows == 0 || b.f6) && (a.rows != 0 || b.rows != 0) && (a.rows ? a.backend : b.backend) == kFP8) {
             const size_t nA = a.rows ? ((a.rows + 63) / 64) * (a.kp / 128) : 0, nB = b.rows ? ((b.rows + 63) / 64) * (b.kp / 128) : 0;
             if (nA + nB > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
-            hipLaunchKernelGGL(quantise_f6_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
+            if (a.xp || b.xp) hipLaunchKernelGGL(quantise_f6_ptr_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
+            else hipLaunchKernelGGL(quantise_f6_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
             return hipGetLastError();
         }
     }
     const size_t nA = stage_blocks<T, MODE_MOD>(kmA, a), nB = stage_blocks<T, MODE_MOD>(kmB, b);
     if (nA + nB == 0) return hipSuccess;
     if (nA + nB > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(quantise_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
+    if (a.xp || b.xp) hipLaunchKernelGGL(quantise_ptr_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
+    else hipLaunchKernelGGL(quantise_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, (int)kmA, (int)kmB);
     return hipGetLastError();
 }
 
@@ -1434,6 +1490,7 @@ unsigned amax_parts_for(size_t rows, size_t k, size_t max_parts) {
 static StageArgs extract_args(int backend, size_t k, size_t kp, const ExtractOperand& o) {
     StageArgs a{};
     a.bx = o.xstride;
+    a.xp = o.xptr;
     a.bw = g_batch.ws;
     a.X = o.X;
     a.ld = o.ld;
@@ -1461,7 +1518,10 @@ template <typename T> static hipError_t launch_amax_pair_t(hipStream_t stream, s
     const size_t nA = (size_t)a.row_groups * a.parts, nB = (size_t)b.row_groups * b.parts;
     if (nA + nB == 0) return hipSuccess;
     if (nA + nB > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(amax_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, k, g_batch.ws);
+    if (A.xptr || B.xptr) {
+        const AmaxPtrOperand pa{a, A.xptr}, pb{b, B.xptr};
+        hipLaunchKernelGGL(amax_ptr_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, pa, pb, (unsigned)nA, k, g_batch.ws);
+    } else hipLaunchKernelGGL(amax_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, k, g_batch.ws);
     return hipGetLastError();
 }
 // an operand in symmetric form (ExtractOperand::sym / QuantOperand::sym): the *_sym_pair launches at the end of this file
@@ -1497,7 +1557,8 @@ template <typename T> static hipError_t launch_extract_pair_t(hipStream_t stream
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL(extract_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, kmA, kmB);
+    if (a.xp || b.xp) hipLaunchKernelGGL(extract_ptr_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, kmA, kmB);
+    else hipLaunchKernelGGL(extract_pair_kernel<T>, dim3((unsigned)(nA + nB), 1, g_batch.batch), dim3(256), 0, stream, a, b, (unsigned)nA, kmA, kmB);
     return hipGetLastError();
 }
 // where the one-read panel body (stage_panel_body) exists: real types, INT8 planes, a single GEMM, k within the step table
@@ -1524,6 +1585,7 @@ hipError_t launch_extract_pair(hipStream_t stream, int dtype, int backend, size_
 static StageArgs quantise_args(int backend, int t_begin, int t_end, size_t k, size_t kp, const QuantOperand& o) {
     StageArgs a{};
     a.bx = o.xstride;
+    a.xp = o.xptr;
     a.bw = g_batch.ws;
     a.X = o.X;
     a.ld = o.ld;
@@ -1870,11 +1932,25 @@ struct ShiftOperand {
     unsigned blocks;
     int kmajor;
 };
+// the operand of fast_shift_ptr_pair_kernel (a pointer-array batch): non-null xp = item z's operand is xp[z].  A type of its own: ShiftOperand keeps its layout.
+struct ShiftPtrOperand : ShiftOperand {
+    const void* const* xp;
+};
 template <typename T> __global__ void __launch_bounds__(256) fast_shift_pair_kernel(const ShiftOperand a, const ShiftOperand b, size_t k, float log2P, size_t bw) {
     const bool isB = blockIdx.x >= a.blocks;
     const ShiftOperand& o = isB ? b : a;  // (kernel arguments: a scalar select per field, no copy)
     const unsigned bid = isB ? blockIdx.x - a.blocks : blockIdx.x;
     const T* X = (const T*)((const char*)o.X + blockIdx.z * o.bx);  // batched launch: item blockIdx.z
+    int16_t* sft = (int16_t*)((char*)o.sft + blockIdx.z * bw);
+    if (o.kmajor) fast_shift_kmajor_body<T>(X, o.ld, k, sft, log2P, bid);
+    else fast_shift_strided_body<T>(X, o.ld, o.rows, k, sft, log2P, bid);
+}
+// the same for a pointer-array batch: the item's operand from ShiftOperand::xp where the operand has an array
+template <typename T> __global__ void __launch_bounds__(256) fast_shift_ptr_pair_kernel(const ShiftPtrOperand a, const ShiftPtrOperand b, size_t k, float log2P, size_t bw) {
+    const bool isB = blockIdx.x >= a.blocks;
+    const ShiftPtrOperand& o = isB ? b : a;
+    const unsigned bid = isB ? blockIdx.x - a.blocks : blockIdx.x;
+    const T* X = (const T*)item_base<true>(o.X, o.xp, o.bx);
     int16_t* sft = (int16_t*)((char*)o.sft + blockIdx.z * bw);
     if (o.kmajor) fast_shift_kmajor_body<T>(X, o.ld, k, sft, log2P, bid);
     else fast_shift_strided_body<T>(X, o.ld, o.rows, k, sft, log2P, bid);
@@ -1898,11 +1974,18 @@ hipError_t launch_fast_shift_pair(hipStream_t stream, int dtype, int backend, un
     if (A.rows + B.rows > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     const ShiftOperand a = operand(A), b = operand(B);
     dim3 grid(a.blocks + b.blocks, 1, g_batch.batch);
+    const ShiftPtrOperand pa{a, A.xptr}, pb{b, B.xptr};
+#define OZ2_FAST_SHIFT(T)                                                                                                           \
+    do {                                                                                                                            \
+        if (A.xptr || B.xptr) hipLaunchKernelGGL(fast_shift_ptr_pair_kernel<T>, grid, dim3(256), 0, stream, pa, pb, k, log2P, g_batch.ws); \
+        else hipLaunchKernelGGL(fast_shift_pair_kernel<T>, grid, dim3(256), 0, stream, a, b, k, log2P, g_batch.ws);                  \
+    } while (0)
     switch (dtype) {
-    case kF32: hipLaunchKernelGGL(fast_shift_pair_kernel<float>, grid, dim3(256), 0, stream, a, b, k, log2P, g_batch.ws); break;
-    case kF64: hipLaunchKernelGGL(fast_shift_pair_kernel<double>, grid, dim3(256), 0, stream, a, b, k, log2P, g_batch.ws); break;
-    case kC32: hipLaunchKernelGGL(fast_shift_pair_kernel<float2>, grid, dim3(256), 0, stream, a, b, k, log2P, g_batch.ws); break;
-    case kC64: hipLaunchKernelGGL(fast_shift_pair_kernel<double2>, grid, dim3(256), 0, stream, a, b, k, log2P, g_batch.ws); break;
+    case kF32: OZ2_FAST_SHIFT(float); break;
+    case kF64: OZ2_FAST_SHIFT(double); break;
+    case kC32: OZ2_FAST_SHIFT(float2); break;
+    case kC64: OZ2_FAST_SHIFT(double2); break;
+#undef OZ2_FAST_SHIFT
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

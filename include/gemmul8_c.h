@@ -139,6 +139,26 @@ GEMMUL8_API int gemmul8_gemm_batched(void *stream, int dtype, int backend, int o
                          long long strideB, const void *beta, void *C, size_t ldc, long long strideC, size_t batch,
                          unsigned num_moduli, int fastmode, void *work);
 
+/* The same batch with the items' addresses in three POINTER ARRAYS (hipblas{S,D,C,Z}gemmBatched): item b is
+ * C_array[b] = alpha * op(A_array[b]) * op(B_array[b]) + beta * C_array[b], all items of one shape, lda / ldb / ldc, alpha and beta.
+ *   - A_array, B_array, C_array hold `batch` pointers each in DEVICE-accessible memory.  They are read by the kernels in stream order (each
+ *     item's workgroups load their own entries), never by the host: no copy back, no synchronisation, capturable in a HIP graph.
+ *   - `work` is the strided form's workspace (gemmul8_work_size_batched); argument checks, the k limits (2^17; FP8: 65536), degenerate sizes
+ *     (m, n, k or batch == 0: GEMMUL8_OK, nothing touched) and the 65535-item launch chunks are those of gemmul8_gemm_batched, in the same order.
+ *     Both backends, both modes, both non-finite modes.
+ *   - The result is bit-identical to `batch` calls of gemmul8_gemm on the items.
+ *   - Items may share or alias A and B (the same pointer many times is the broadcast case).  The C windows must not overlap each other or
+ *     any A / B.  Nothing outside the m x n windows of C is written.
+ *   - Each item pointer needs the alignment of its element type only (16-byte forms are chosen per item inside the kernels).
+ *   - Item pointers are NOT validated: the library cannot tell a null or dangling entry from a valid one, a kernel will simply use it.
+ *   - The arrays must stay unchanged until the call's kernels have run.  Under graph capture they are read at every REPLAY: what the
+ *     arrays hold then is what the replay computes on.
+ * No counterpart in the reference. */
+GEMMUL8_API int gemmul8_gemm_batched_ptr(void *stream, int dtype, int backend, int op_A, int op_B, size_t m, size_t n, size_t k,
+                         const void *alpha, const void *const *A_array, size_t lda, const void *const *B_array, size_t ldb,
+                         const void *beta, void *const *C_array, size_t ldc, size_t batch, unsigned num_moduli, int fastmode,
+                         void *work);
+
 /* Symmetric rank-k update of one triangle: C = alpha*A*A^T + beta*C (trans = N, A is n x k) or C = alpha*A^T*A + beta*C (trans = T, A is
  * k x n; for the complex types too this is the plain transpose: SYRK, not HERK).  trans takes 0 / 1 or the hipblasOperation_t values 111 / 112,
  * uplo GEMMUL8_LOWER / GEMMUL8_UPPER or the hipblasFillMode_t values 122 / 121.  All four element types, INT8 backend only (GEMMUL8_FP8:
