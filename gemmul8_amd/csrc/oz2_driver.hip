@@ -103,6 +103,7 @@ static Knobs parse_knobs() {
         k.crt_panels = std::min(atoi(e), 256);
         k.crt_panels_ring = e[strlen(e) - 1] == 'r';
     }
+    if (const char* e = getenv("GEMMUL8_GEMM_SBS"); e && (e[0] == '0' || e[0] == '1')) k.gemm_sbs = e[0] - '0';
     if (const char* e = getenv("GEMMUL8_MAP_COLBLOCK"); e && *e) k.map_colblock = atoi(e) > 0 ? atoi(e) : 0;
     return k;
 }

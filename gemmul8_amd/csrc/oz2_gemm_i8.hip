@@ -58,6 +58,12 @@ namespace oz2 {
 #ifndef OZ2_KBAR_MAX_KP
 #define OZ2_KBAR_MAX_KP 5120  // padded k up to which the K-step-barrier schedule is used (see launch<EPI>); 0 = never, 1 << 30 = always.  Round 4 (after the epilogue / tile-prologue work): +1.0 / +1.3 % at k = 4608 / 5120 on 8192^2 x 14 planes, +0.5 % at 5120 on 16384^2 x 6; at 6144 +0.9 % / -1.1 %, at 7168 0 / -1.3 %, at 8192 -1.3 % (profiles/archive/r04_gemm_ab_kbar_threshold.txt)
 #endif
+#ifndef OZ2_SBS_DEFAULT
+#define OZ2_SBS_DEFAULT 1  // whether the residue launches of the ping-pong schedule take gemm_i8_sbs_kernel when GEMMUL8_GEMM_SBS is unset (see launch<EPI>)
+#endif
+#ifndef OZ2_SBS_MAX_TILES
+#define OZ2_SBS_MAX_TILES 1024  // ... for planes of at most this many 256 x 256 tiles.  Interleaved against the parent build, 14 planes of a real quantise pass, 25 pairs: 8192^2 x 6144 / 8192 launch -1.68 / -1.31 % (22 / 7.5 s.e.), whole call 8192^2 x 6144 / 8192 -1.35 / -0.98 % (16 / 10.5 s.e.); 16384^2 x 8192 (4096 tiles) launch +0.85 % SLOWER (5.5 s.e.; +0.39 % on a second box): off there (profiles/r10_sbs_epilogue_ab.txt)
+#endif
 #ifndef OZ2_SLEEP_A
 #define OZ2_SLEEP_A 4  // s_sleep units (64 clocks) between the A producers' 8 groups of 2 LDS-DMA instructions
 #endif
@@ -104,10 +110,22 @@ template <bool ZERO> struct MfmaReinitHook {  // ZERO: the start value is 0 (sho
 };
 // SMALLK: the launch has K <= 512 (accumulators start at 0, three-instruction residue); the epilogue form is a compile-time property of the kernel
 #define OZ2_I8_KR 0
+#define OZ2_I8_SBS 0
 #define OZ2_I8_KERNEL_HEAD                                       \
     template <int EPI, bool KBAR, int FUSE, bool SMALLK = false> \
     __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kernel(const GemmArgs args, const std::conditional_t<FUSE != 0, CrtArgs, NoCrt> crt)
 #include "oz2_gemm_i8_kernel.inc"
+#undef OZ2_I8_KERNEL_HEAD
+// The ping-pong schedule with the two wave halves' tile epilogues SIDE BY SIDE (see OZ2_I8_SBS in the kernel text): the residue launch above
+// OZ2_KBAR_MAX_KP takes it (launch<EPI_MOD>, GEMMUL8_GEMM_SBS).  A kernel of its own name, <EPI_MOD, false, 0, false> its only instantiation.
+#undef OZ2_I8_SBS
+#define OZ2_I8_SBS 1
+#define OZ2_I8_KERNEL_HEAD                               \
+    template <int EPI, bool KBAR, int FUSE, bool SMALLK> \
+    __global__ void __launch_bounds__(WS_THREADS) gemm_i8_sbs_kernel(const GemmArgs args, const NoCrt crt)
+#include "oz2_gemm_i8_kernel.inc"
+#undef OZ2_I8_SBS
+#define OZ2_I8_SBS 0
 #undef OZ2_I8_KR
 #undef OZ2_I8_KERNEL_HEAD
 // The K-RANGED form of the same kernel (gemmul8_trmm; krange = a KRange of oz2_gemm_common.hpp, never 0): a tile runs only the K-steps [k0, k1) of its
@@ -123,6 +141,7 @@ template <bool ZERO> struct MfmaReinitHook {  // ZERO: the start value is 0 (sho
     __global__ void __launch_bounds__(WS_THREADS) gemm_i8_kr_kernel(const GemmArgs args, const NoCrt crt, const int krange)
 #include "oz2_gemm_i8_kernel.inc"
 #undef OZ2_I8_KR
+#undef OZ2_I8_SBS
 #undef OZ2_I8_KERNEL_HEAD
 
 static void fill_common(GemmArgs& a, size_t kp, size_t m, size_t n) {
@@ -151,7 +170,7 @@ static int num_cus() {
     return n;
 }
 
-template <int EPI, bool KBAR, int FUSE = 0, bool SMALLK = false, bool KR = false>
+template <int EPI, bool KBAR, int FUSE = 0, bool SMALLK = false, bool KR = false, bool SBS = false>
 static hipError_t launch_sched(hipStream_t stream, GemmArgs& a, const std::conditional_t<FUSE != 0, CrtArgs, NoCrt>& crt = {}, [[maybe_unused]] int krange = 0) {
     // the attribute belongs to the function on ONE device; setting it is idempotent, so concurrent first calls from several host
     // threads only need the flag itself to be race-free
@@ -161,6 +180,7 @@ static hipError_t launch_sched(hipStream_t stream, GemmArgs& a, const std::condi
     if (!attr_set_dev[dev_].load(std::memory_order_acquire)) {
         const void* fn;
         if constexpr (KR) fn = (const void*)gemm_i8_kr_kernel<EPI, KBAR, FUSE, SMALLK>;
+        else if constexpr (SBS) fn = (const void*)gemm_i8_sbs_kernel<EPI, KBAR, FUSE, SMALLK>;
         else fn = (const void*)gemm_i8_kernel<EPI, KBAR, FUSE, SMALLK>;
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES);
         if (e != hipSuccess) return e;
@@ -174,6 +194,7 @@ static hipError_t launch_sched(hipStream_t stream, GemmArgs& a, const std::condi
     if (grid <= 0) grid = 8;
     if (a.total_tiles < grid) grid = a.total_tiles;
     if constexpr (KR) hipLaunchKernelGGL((gemm_i8_kr_kernel<EPI, KBAR, FUSE, SMALLK>), dim3(grid), dim3(WS_THREADS), RING_LDS_BYTES, stream, a, crt, krange);
+    else if constexpr (SBS) hipLaunchKernelGGL((gemm_i8_sbs_kernel<EPI, KBAR, FUSE, SMALLK>), dim3(grid), dim3(WS_THREADS), RING_LDS_BYTES, stream, a, crt);
     else hipLaunchKernelGGL((gemm_i8_kernel<EPI, KBAR, FUSE, SMALLK>), dim3(grid), dim3(WS_THREADS), RING_LDS_BYTES, stream, a, crt);
     return hipGetLastError();
 }
@@ -213,6 +234,11 @@ template <int EPI> static hipError_t launch(hipStream_t stream, GemmArgs& a, int
         }
         if (a.acc0 == 0) return launch_sched<EPI, true, 0, true>(stream, a);  // K <= 512
         if (a.kp * a.nseg <= OZ2_KBAR_MAX_KP) return launch_sched<EPI, true>(stream, a);
+    }
+    // the ping-pong schedule.  Its residue launch (any tile walk) has a second form, the two halves' epilogues side by side (gemm_i8_sbs_kernel):
+    // GEMMUL8_GEMM_SBS=0|1 forces one of them, bit-identical planes (tests/test_gpu_gemm_sbs.py)
+    if constexpr (EPI == EPI_MOD) {
+        if (const int sbs = knobs().gemm_sbs; sbs == 1 || (sbs < 0 && OZ2_SBS_DEFAULT && a.tiles_m * a.tiles_n <= OZ2_SBS_MAX_TILES)) return launch_sched<EPI_MOD, false, 0, false, false, true>(stream, a);
     }
     return launch_sched<EPI, false>(stream, a);
 }

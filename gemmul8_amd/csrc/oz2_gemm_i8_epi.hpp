@@ -30,7 +30,10 @@ namespace oz2 {
 #ifndef OZ2_HOOK_SKIP_EPILOGUE
 #define OZ2_HOOK_SKIP_EPILOGUE 0          // consumers: 1 = keep the accumulators live, no epilogue
 #endif
-#if defined(OZ2_PRODUCT_BUILD) && OZ2_HOOK_SKIP_EPILOGUE
+#ifndef OZ2_HOOK_SKIP_EPILOGUE_HALF
+#define OZ2_HOOK_SKIP_EPILOGUE_HALF 0     // consumers, ping-pong schedule: mask of the wave halves (bit wm) that run no epilogue
+#endif
+#if defined(OZ2_PRODUCT_BUILD) && (OZ2_HOOK_SKIP_EPILOGUE || OZ2_HOOK_SKIP_EPILOGUE_HALF)
 #error "timing probes (OZ2_HOOK_SKIP_*) compute something else: not allowed in the product build of libgemmul8.so"
 #endif
 

@@ -1,7 +1,9 @@
 // The body of the persistent residue / bound GEMM kernel, included by oz2_gemm_i8.hip once per kernel NAME behind the includer's template head and
 // signature (OZ2_I8_KERNEL_HEAD): gemm_i8_kernel with OZ2_I8_KR 0 -- the text every launch before gemmul8_trmm compiled, token for token -- and
 // gemm_i8_kr_kernel with OZ2_I8_KR 1, the K-ranged form (see there).  Everything the K ranges add sits behind #if OZ2_I8_KR or in a hook macro that is
-// empty without it.
+// empty without it.  gemm_i8_sbs_kernel with OZ2_I8_SBS 1 is the ping-pong schedule with the two halves' epilogues SIDE BY SIDE: the lagging half
+// (wm = 1) takes the last barrier of a tile -- the one behind the MFMAs of segment (ks2, ah) = (1, 1) of the tile's last K-step -- behind its epilogue
+// and the next tile's accumulator initialisation instead of in front of them (behind #if OZ2_I8_SBS; everything else is the same text).
 OZ2_I8_KERNEL_HEAD {
 #ifndef OZ2_LAB_FUSED_CRT
     static_assert(FUSE == 0, "the in-kernel CRT forms are laboratory code: tools/experiments/fused_crt");
@@ -279,6 +281,16 @@ OZ2_I8_KERNEL_HEAD {
     __builtin_amdgcn_s_barrier();               // K-tile 0 published by the producers
     if (wm == 1) __builtin_amdgcn_s_barrier();  // trailing half: one segment behind
     int sA = 0;                                  // slot of A(g); B(g) sits in the next slot (mod 5)
+#if OZ2_I8_SBS
+    // Epilogues side by side.  With G the barrier behind the leading half's last MFMA segment of a tile, that half reduces and stores between G and G + 1;
+    // the lagging half has its last 16 MFMAs there and, in gemm_i8_kernel, arrives at G + 1 right behind them, so that ITS epilogue runs between G + 1
+    // and G + 2 -- beside 16 MFMAs of the leading half, which then waits at G + 2: the two epilogues are serialised and both are exposed.  Here the
+    // lagging half arrives at G + 1 only behind its epilogue and the next tile's accumulator initialisation: both halves reduce and store between the same
+    // two barriers, and from G + 1 on the anti-phase is the old one.  Every wave executes the same barriers as before, one of them later: the epilogue
+    // touches no LDS, the half's reads of the tile's last K-step are complete before its last MFMAs (the ring's WAR rule holds as it is), and the
+    // producers only wait longer at G + 1, the next tile's first panels already in flight.  tests/test_gemm_sbs_barrier_model.py replays both orders.
+    static_assert(EPI == EPI_MOD && !KBAR && FUSE == 0 && !SMALLK && !OZ2_I8_KR, "side-by-side epilogues: the residue launch of the ping-pong schedule, one phase per tile");
+#endif
     for (int vb = blockIdx.x; vb < total; vb += G) {
         const TileMap tmap = OZ2_I8_MAP_TILE(vb);
         const PlaneRef pref = (FUSE || EPI == EPI_MAX) ? PlaneRef{0, 0} : plane_ref(args, tmap.plane);  // (the bound GEMM looks its plane up at the epilogue: one value less across its K loop)
@@ -290,57 +302,38 @@ OZ2_I8_KERNEL_HEAD {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 acc[i][j] = v4i{EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0, EPI == EPI_MAX ? 0 : args.acc0};
+#if OZ2_I8_SBS
+        if (wm == 1 && vb != (int)blockIdx.x) {  // the previous tile's last barrier: behind its epilogue and this initialisation
+#pragma unroll
+            for (int i = 0; i < 8; ++i)  // (opaque uses: the v_mov_b32 are not sunk behind the barrier)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(acc[i][j]));
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
 
         int kt = 0;  // phases: see the K-step-barrier branch
         const int nph = (EPI == EPI_MAX && args.kt_mid > 0) ? 2 : 1;
         for (int ph = 0; ph < nph; ++ph) {
         const int kt_end = (EPI == EPI_MAX && ph + 1 < nph) ? args.kt_mid : OZ2_I8_KSTEPS(tmap);
+#define OZ2_I8_PP_DEFER 0
+#if OZ2_I8_SBS
+        for (; kt < kt_end - wm; ++kt) {  // the lagging half's last K-step of the tile is peeled: a tile has K-steps (kp >= 256)
+#else
         for (; kt < kt_end; ++kt) {
-            const char* curA = smem + sA * TILE_BYTES + a_base;
-            const char* curB = smem + (sA == 4 ? 0 : sA + 1) * TILE_BYTES + b_base;
-            sA = sA + 2 >= 5 ? sA - 3 : sA + 2;
-#pragma unroll
-            for (int ks2 = 0; ks2 < 2; ++ks2) {
-                const int coff = (((ks2 << 2) | q) ^ sw) << 4;
-                v4i bf[4];
-#pragma unroll
-                for (int ah = 0; ah < 2; ++ah) {
-                    v4i af[4];
-                    if (ah == 0) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            bf[j] = *(const v4i*)(curB + j * 16 * BK + coff);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        af[i] = *(const v4i*)(curA + (ah * 4 + i) * 16 * BK + coff);
-                    // Only the K-step's LAST load segment completes its reads BEFORE the barrier: that is the barrier the ring's WAR rule counts on
-                    // (LDS operations of a wave complete in order, so its wait covers every read of the K-step).  The other three segments arrive at
-                    // the barrier as soon as their reads are ISSUED and wait behind it: a wave's LDS latency no longer delays the hand-over of all
-                    // twelve (+0.4 / +0.5 % at k = 6144 / 8192, planes bit-identical: profiles/archive/r04e_late_wait_ab.txt)
-                    if (ks2 == 1 && ah == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (!(ks2 == 1 && ah == 1)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_setprio(1);
-                    // serpentine order over the 4 x 4 fragment pairs: consecutive MFMAs share an operand register also across the row change
-                    // (B fragment 3, 3, 0, 0 ...): +0.5 ... 0.65 % at k >= 8192, interleaved (profiles/archive/r04_gemm_ab_serpentine_kbar.txt)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            const int j = (i & 1) ? 3 - jj : jj;
-                            acc[ah * 4 + i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[j], acc[ah * 4 + i][j], 0, 0, 0);
-                        }
-                    __builtin_amdgcn_s_setprio(0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+#endif
+#include "oz2_gemm_i8_pp_kstep.inc"
         }
+#undef OZ2_I8_PP_DEFER
+#if OZ2_I8_SBS
+        if (wm == 1) {  // ... without the barrier behind its last MFMA segment
+#define OZ2_I8_PP_DEFER 1
+#include "oz2_gemm_i8_pp_kstep.inc"
+#undef OZ2_I8_PP_DEFER
+        }
+#endif
 #if OZ2_HOOK_SKIP_EPILOGUE
         (void)tmap;  // laboratory probe: no epilogue; the accumulators stay live
 #pragma unroll
@@ -351,10 +344,28 @@ OZ2_I8_KERNEL_HEAD {
         // every reload still pending on some path is waited for HERE (the previous tile's stores retired a whole K loop ago: free), so that the waitcnt
         // pass has no reason to put a vmcnt wait into the K loop (it did, in the K-step-barrier kernels until round 4 and in the bound GEMM after a
         // register-allocation change: tests/test_kernel_resources.py)
+#if OZ2_HOOK_SKIP_EPILOGUE_HALF
+        if ((OZ2_HOOK_SKIP_EPILOGUE_HALF >> wm) & 1) {  // laboratory probe: no epilogue on this half
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
+        } else
+#endif
+        {
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+#if OZ2_I8_SBS
+        // the epilogue's lane id is recomputed behind an opaque asm, as in the K-step-barrier branch: with the peeled K-step a lane-derived value of the
+        // epilogue was otherwise kept in scratch across the K loop (8 bytes)
+        int lane_e;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+        i8_epilogue<EPI, NoHook, (int)SMALLK>(acc, args, pref, pcon, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane_e);
+#else
         if constexpr (FUSE != 0) i8_epilogue<EPI, NoHook, -1>(acc, args, PlaneRef{0, pl}, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane);
         else if constexpr (EPI == EPI_MAX) i8_epilogue<EPI, NoHook, 0>(acc, args, plane_ref(args, tmap.plane), PlaneConsts{}, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane);
         else i8_epilogue<EPI, NoHook, (int)SMALLK>(acc, args, pref, pcon, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane);
+#endif
+        }
 #endif
         }  // phase
         }
@@ -362,6 +373,9 @@ OZ2_I8_KERNEL_HEAD {
         if constexpr (FUSE != 0) i8_crt_tail<std::conditional_t<FUSE == 2, float, double>>(args, tmap.tm * BM + wm * 128, tmap.tn * BN + wn * 64, lane);
 #endif
     }
+#if OZ2_I8_SBS
+    if (wm == 1 && (int)blockIdx.x < total) __builtin_amdgcn_s_barrier();  // the last tile's last barrier
+#endif
     if (wm == 0) __builtin_amdgcn_s_barrier();
     }
 }

@@ -19,7 +19,8 @@ struct Knobs {
     int crt_panels_ring = 0;
     int scale_fold = 1;            // GEMMUL8_SCALE_FOLD=0: accurate mode's zero-fill, two extracts and shift finalize as launches of their own (9 launches) instead of the extract-pair launch that also zero-fills and the quantise launch that also finalizes (6)
     int bounds_one_read = -1;      // GEMMUL8_BOUNDS_ONE_READ=0|1: accurate mode's bound plane of a row-strided operand after a row-maxima pass (0) / from one read of the operand wherever that form exists (1) (-1: by row count)
-    int map_colblock = -1;         // GEMMUL8_MAP_COLBLOCK=<w>: tile-columns per column block of the GEMM tile walk, 0 = full width (-1: map_colblock's rule)
+    int gemm_sbs = -1;             // GEMMUL8_GEMM_SBS=0|1: residue launches of the ping-pong schedule (k > 5120) with the wave halves' tile epilogues serialised, gemm_i8_kernel (0) / side by side, gemm_i8_sbs_kernel (1) (-1: the launch rule's default, oz2_gemm_i8.hip)
+    int map_colblock = -1;        // GEMMUL8_MAP_COLBLOCK=<w>: tile-columns per column block of the GEMM tile walk, 0 = full width (-1: map_colblock's rule)
 };
 const Knobs& knobs();  // oz2_driver.hip
 void reload_knobs();

@@ -6,6 +6,8 @@
 //   8   no epilogue, the accumulators stay live
 //   16  operands come from the first 8 K-steps of a panel only (every fetch an L2 hit: what the L2 misses cost)
 //   64  the epilogue without its stores (what the store path costs at short k)
+//   128 / 256  ping-pong schedule: no epilogue on the leading (wm = 0) / lagging (wm = 1) wave half.  Whether the two halves' epilogues are serialised:
+//       then each bit alone saves about one epilogue per tile and both together two; side by side (gemm_i8_sbs_kernel) one bit alone saves little
 //   32  dose-response of the operand path: after a workgroup's first tile the LDS-DMA of every OZ2_DMA_SKIP-th K-step is left out
 //       (OZ2_DMA_SKIP = 6: -16.7 % of the L2 -> LDS bytes per MAC, what a 384 x 256 CU tile would save; 2: -50 %)
 // OZ2_KSTAG=<1..4> staggers the K-step a workgroup starts from (1: XCD x starts at x KT1 / 8; 2: plus (CU & 3) K-steps; 3: (CU & 7)
@@ -29,8 +31,11 @@
 #if OZ2_PROBE & 8
 #define OZ2_HOOK_SKIP_EPILOGUE 1
 #endif
+#if OZ2_PROBE & (128 | 256)
+#define OZ2_HOOK_SKIP_EPILOGUE_HALF ((OZ2_PROBE >> 7) & 3)
+#endif
 #if OZ2_PROBE & 64
-#define OZ2_HOOK_SKIP_STORES 1  // round 6: the residue epilogue's arithmetic, transposes and address work, but no global_store
+#define OZ2_HOOK_SKIP_STORES 1 // round 6: the residue epilogue's arithmetic, transposes and address work, but no global_store
 #endif
 #if OZ2_PROBE & 16
 #define OZ2_HOOK_KSTEP(kin) ((kin) & 7)

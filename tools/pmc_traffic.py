@@ -64,7 +64,7 @@ if len(sys.argv) > 6 and sys.argv[6] == "fp8":   # config 3: SGEMM n^3, N moduli
 out = {}
 for k in sorted(set(fetch) | set(write)):
     f_kib, w_kib = fetch.get(k, 0.0), write.get(k, 0.0)
-    if "gemm_i8_kernel" in k or "gemm_f8_kernel" in k or "gemm_f6_kernel" in k:
+    if "gemm_i8_kernel" in k or "gemm_i8_sbs_kernel" in k or "gemm_i8_kr_kernel" in k or "gemm_f8_kernel" in k or "gemm_f6_kernel" in k:
         corr, why = 2.0, "16 B/lane LDS-DMA reads (guide)"
     elif "crt_kernel<float" in k and f_kib > 0 and len(sys.argv) > 6:   # the N int16 residue planes, read once (beta = 0)
         ratio = N * n * n * 2.0 / (f_kib * 1024.0)
