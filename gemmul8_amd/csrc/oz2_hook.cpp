@@ -11,17 +11,10 @@
 //   hipblas{S,D,C,Z}gemmStridedBatched, hipblasGemmStridedBatchedEx         yes (torch.bmm): no early out, degenerate calls are the native routine's
 //   hipblas{S,D,C,Z}gemmBatched(_64), hipblasGemmBatchedEx(_64),            yes (pointer arrays in device memory): one set of launches through gemmul8_gemm_batched_ptr, the
 //     hipblasGemmBatchedExWithFlags(_64)                                      arrays are never read on the host; no per-item fallback, see emulate_batch_ptr
-//   hipblas{S,D,C,Z}syrk(_64), hipblas{C,Z}herk(_64)                        yes: one triangle through gemmul8_syrk / gemmul8_herk (INT8 backend, k <= 2^17; HERK: real
-//                                                                             alpha / beta, N / C only); everything else is the native routine's, see try_syrk_impl
-//   hipblas{S,D,C,Z}syr2k(_64)                                              yes: one triangle through gemmul8_syr2k (INT8 backend, k <= 2^16, N / T only); see try_syrk_impl
-//   hipblas{C,Z}her2k(_64)                                                  yes: one triangle through gemmul8_her2k (INT8 backend, k <= 2^17, N / C only; complex alpha,
-//                                                                             real beta); see try_syrk_impl
-//   hipblas{S,D,C,Z}symm(_64), hipblas{C,Z}hemm(_64)                        yes: the product with a symmetric / Hermitian matrix through gemmul8_symm / gemmul8_hemm (INT8 backend,
-//                                                                             order of A <= 2^17; one triangle of A read in place); see try_symm_impl
-//   hipblas{S,D,C,Z}trmm(_64)                                               yes: the product with a triangular matrix (ROCm 7's out-of-place signature) through gemmul8_trmm
-//                                                                             (INT8 backend, order of A <= 2^17; the triangle read in place); see try_trmm_impl
-//   hipblas{S,D,C,Z}trsm(_64)                                               yes: the triangular solve, in place on B, through gemmul8_trsm (INT8 backend, order of A
-//                                                                             <= 2^17; recursive blocking, emulated GEMM updates); see try_trsm_impl
+//   hipblas{S,D,C,Z}syrk(_64), hipblas{C,Z}herk(_64),                       yes: the Level-3 routines beyond GEMM, each through its gemmul8_* entry point (INT8 backend only), everything
+//     hipblas{S,D,C,Z}syr2k(_64), hipblas{C,Z}her2k(_64),                     the emulation does not take is the native routine's; one gate for the eight, see try_level3:
+//     hipblas{S,D,C,Z}symm(_64), hipblas{C,Z}hemm(_64),                       one triangle of C for the rank-k four (k <= 2^17, SYR2K: 2^16), one triangle of A read in place for
+//     hipblas{S,D,C,Z}trmm(_64), hipblas{S,D,C,Z}trsm(_64)                    SYMM / HEMM / TRMM (ROCm 7's out-of-place signature) / TRSM (in place on B), order of A <= 2^17
 //   hipblasLtMatmul, hipblasLtDestroy                                       yes (PyTorch's float32 matmuls): the plain case only, see lt_try
 //   hipblasLtMatrixLayoutCreate / SetAttribute / Destroy                    yes: record what a layout holds (hipBLASLt cannot be asked)
 //   rocblas_{s,d,c,z}gemm, rocblas_{s,d,c,z}gemm_strided_batched,           yes, only with GEMMUL8_HOOK_ROCBLAS=1: applications that call rocBLAS directly
@@ -40,10 +33,10 @@
 //                                  once        workspace pre-sizing, applied when a SKIP_SCALE switch is on (hook.cu:232-281,656-662)
 //  the rest is this build's only:
 //   GEMMUL8_FP8_BOUND, GEMMUL8_NONFINITE
-//                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace); under `ieee` SYRK / HERK / SYR2K / HER2K
-//                                              calls are not emulated (try_syrk_impl), nor are SYMM / HEMM (try_symm_impl), TRMM (try_trmm_impl) and TRSM calls (try_trsm_impl)
+//                                  once        `reference` / `ieee`: gemmul8_set_fp8_bound_mode / gemmul8_set_nonfinite_mode (init_max_workspace); under `ieee` the Level-3
+//                                              routines beyond GEMM are not emulated (try_level3)
 //   GEMMUL8_MIN_FLOPS              per call    unset or 0 = emulate every selected call (the reference's behaviour); `auto` = a fitted cost model decides
-//                                              per call (below_floor); a number = floor on 2*m*n*k.  The first call a floor declines is logged once.
+//                                              per call (below_floor; level3_below_floor); a number = floor on 2*m*n*k.  The first call a floor declines is logged once.
 //   GEMMUL8_DIST                   per call    blocks | moduli | fp64sum: shard every emulated GEMM over the ranks of an SPMD job (try_dist)
 //   GEMMUL8_BATCH_FUSED, GEMMUL8_BATCH_WORKSPACE_MB, GEMMUL8_BATCH_STREAMS
 //                                  per call    strided batches: one set of launches (default) in chunks of the given size, or lanes (emulate_batch)
@@ -360,7 +353,7 @@ void init_max_workspace() {
             if (!std::strcmp(fb, "reference")) (void)abi().set_fp8_bound_mode(1);
         // GEMMUL8_NONFINITE=ieee: BLAS-like NaN / Inf propagation (include/gemmul8_c.h, gemmul8_set_nonfinite_mode); unset or `reference`: mode 0.
         // Not applied to the calls the multi-GPU plans take (GEMMUL8_DIST).
-        // The rank-k entry points have no mode 1: their calls stay on the native routine under `ieee` (try_syrk_impl).
+        // The rank-k entry points have no mode 1: their calls stay on the native routine under `ieee` (try_level3).
         if (const char* nf = std::getenv("GEMMUL8_NONFINITE"); nf && *nf) {
             if (nonfinite_ieee()) {
                 if (auto set = abi().set_nonfinite_mode) (void)set(1);
@@ -571,20 +564,65 @@ struct NativeScope {
     NativeScope(const NativeScope&) = delete;
     NativeScope& operator=(const NativeScope&) = delete;
 };
-enum { kSYRK = 0, kHERK = 1, kSYR2K = 2, kHER2K = 3, kRankKinds = 4 };  // the rank-k routines of try_syrk
-const char* const kRankName[kRankKinds] = {"SYRK", "HERK", "SYR2K", "HER2K"};
+// ---- the Level-3 routines beyond GEMM (no counterpart in the reference): one table, one call record (Level3Call), one gate (try_level3).
+// Two families.  Rank-k: one triangle of the n x n matrix C from operands with inner dimension k -- SYRK alpha A A^T + beta C, HERK alpha A A^H + beta C
+// (real alpha, beta), SYR2K alpha (A B^T + B A^T) + beta C, HER2K alpha A B^H + conj(alpha) B A^H + beta C (complex alpha, real beta).  Side: B and C are
+// m x n and A, of which one triangle is stored and read in place, has order ka = m (side = left) / n (right) -- SYMM / HEMM alpha A B + beta C or
+// alpha B A + beta C, TRMM C = alpha op(A) B or alpha B op(A) (ROCm 7's out-of-place signature; C == B is gemmul8_trmm's contract), TRSM op(A) X = alpha B
+// or X op(A) = alpha B with X over B.
+enum Routine { kSYRK, kHERK, kSYR2K, kHER2K, kSYMM, kHEMM, kTRMM, kTRSM, kRoutines };  // the order of the statistics lines
+enum Ops { kOpsNT, kOpsNC, kOpsNone, kOpsNTC };  // the operations a routine takes: N / T, N / C, it has no such argument, N / T / C and a diag
+// kTrsmAutoMinOrder: the smallest measured order of A from which the emulated TRSM beats the native one at n = ka in float64 accurate mode
+// (profiles/trsm_ab.json, tools/trsm_ab.py; INTEGRATION.md "TRSM" prints the table): DTRSM left at 14 moduli loses at 8192 x 8192 (25.1 against 19.4 ms) and
+// wins at 16384 x 16384 (88.6 against 108.1 ms).  The rule asks for the order only: it also declines the right-side 8192 x 8192 row, which the emulation wins.
+constexpr int kTrsmAutoMinOrder = 16384;
+struct RoutineInfo {
+    const char* name;    // in the notices and the statistics
+    const char* tag;     // the workspace's name in grow()'s messages
+    bool side;           // the family
+    Ops ops;
+    bool beta, B;        // the pointers required beyond alpha, A and C
+    int limit;           // the largest k (rank-k) / order of A (side) the emulation takes
+    int k_fold;          // rank-k: the GEMM the call amounts to is (n, n, k_fold k) -- SYR2K puts A and B side by side, hence its limit of 2^16; side: (m, n, ka)
+    double floor_flops;  // GEMMUL8_MIN_FLOPS as a number: a floor on floor_flops x n (n + 1) k (rank-k) / m n ka (side), the routine's own count (HER2K's in real operations)
+    int auto_min_order;  // GEMMUL8_MIN_FLOPS=auto: 0 = the GEMM model's decision for that GEMM (no scan of these routines has been fitted; SYRK / HERK, native and
+                         // emulated, are both about half their GEMMs; conservative for TRMM, which does less work than its GEMM); otherwise decline below this order of A
+    double stats_flops;  // GEMMUL8_HOOK_STATS: stats_flops x the same product (x 4 for complex) / 1e6, rounded down
+};
+const RoutineInfo kRoutine[kRoutines] = {
+    {"SYRK", "workC (syrk)", false, kOpsNT, true, false, kMaxK, 1, 1.0, 0, 1.0},
+    {"HERK", "workC (herk)", false, kOpsNC, true, false, kMaxK, 1, 1.0, 0, 1.0},
+    {"SYR2K", "workC (syr2k)", false, kOpsNT, true, true, kMaxK / 2, 2, 2.0, 0, 2.0},
+    {"HER2K", "workC (her2k)", false, kOpsNC, true, true, kMaxK, 1, 8.0, 0, 2.0},
+    {"SYMM", "workC (symm)", true, kOpsNone, true, true, kMaxK, 1, 2.0, 0, 2.0},
+    {"HEMM", "workC (hemm)", true, kOpsNone, true, true, kMaxK, 1, 2.0, 0, 2.0},
+    {"TRMM", "workC (trmm)", true, kOpsNTC, false, true, kMaxK, 1, 1.0, 0, 1.0},
+    {"TRSM", "workC (trsm)", true, kOpsNTC, false, false, kMaxK, 1, 1.0, kTrsmAutoMinOrder, 1.0},
+};
+// One Level-3 call as its hipBLAS entry point received it (GemmCall's role); what a routine does not have stays zero / null
+struct Level3Call {
+    Routine routine;
+    int dtype;
+    int side = 0, uplo = 0, trans = 0, diag = 0;
+    int64_t m = 0, n = 0, k = 0;
+    const void *alpha = nullptr, *A = nullptr;
+    int64_t lda = 0;
+    const void* B = nullptr;
+    int64_t ldb = 0;
+    const void* beta = nullptr;
+    void* C = nullptr;  // the matrix written: TRSM's is hipBLAS's B
+    int64_t ldc = 0;
+    // the product the floor and the statistics scale: n (n + 1) k / m n ka
+    double flops() const {
+        const double dm = (double)m, dn = (double)n;
+        return kRoutine[routine].side ? dm * dn * (side == HIPBLAS_SIDE_RIGHT ? dn : dm) : dn * (dn + 1.0) * (double)k;
+    }
+};
+
 struct HookStats {
     std::atomic<unsigned long long> emu_calls{0}, nat_calls{0};
     std::atomic<unsigned long long> emu_mflops{0}, nat_mflops{0};  // 2 m n k batch / 1e6 (x 4 for complex), rounded down
-    // hipblas?syrk [0] / hipblas?herk [1] / hipblas?syr2k [2] / hipblas?her2k [3]: n (n + 1) k / 1e6 (x 4 for complex; syr2k, her2k: x 2)
-    std::atomic<unsigned long long> emu_syrk[kRankKinds] = {{0}, {0}, {0}, {0}}, nat_syrk[kRankKinds] = {{0}, {0}, {0}, {0}}, emu_syrk_mflops[kRankKinds] = {{0}, {0}, {0}, {0}},
-                                    nat_syrk_mflops[kRankKinds] = {{0}, {0}, {0}, {0}};
-    // hipblas?symm [0] / hipblas?hemm [1]: 2 m n ka / 1e6 (x 4 for complex)
-    std::atomic<unsigned long long> emu_symm[2] = {{0}, {0}}, nat_symm[2] = {{0}, {0}}, emu_symm_mflops[2] = {{0}, {0}}, nat_symm_mflops[2] = {{0}, {0}};
-    // hipblas?trmm: m n ka / 1e6 (x 4 for complex), the routine's own flop count
-    std::atomic<unsigned long long> emu_trmm{0}, nat_trmm{0}, emu_trmm_mflops{0}, nat_trmm_mflops{0};
-    // hipblas?trsm: m n ka / 1e6 (x 4 for complex)
-    std::atomic<unsigned long long> emu_trsm{0}, nat_trsm{0}, emu_trsm_mflops{0}, nat_trsm_mflops{0};
+    std::atomic<unsigned long long> level3[kRoutines][2][2] = {};  // [routine][emulated, native][calls, mflops (RoutineInfo::stats_flops)]
     static void dump();
     HookStats() { std::atexit(&HookStats::dump); }
 };
@@ -597,23 +635,12 @@ void HookStats::dump() {
     HookStats& h = hook_stats();
     std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu GEMM calls (%.3f TFLOP), native %llu GEMM calls through the hooked entry points (%.3f TFLOP)\n",
                  h.emu_calls.load(), h.emu_mflops.load() * 1e-6, h.nat_calls.load(), h.nat_mflops.load() * 1e-6);
-    for (int kind = 0; kind < kRankKinds; ++kind)
-        if (h.emu_syrk[kind].load() + h.nat_syrk[kind].load())
+    for (int r = 0; r < kRoutines; ++r) {  // a line for each routine that was seen
+        const auto& n = h.level3[r];
+        if (n[0][0].load() + n[1][0].load())
             std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu %s calls (%.3f TFLOP), native %llu %s calls through the hooked entry points (%.3f TFLOP)\n",
-                         h.emu_syrk[kind].load(), kRankName[kind], h.emu_syrk_mflops[kind].load() * 1e-6, h.nat_syrk[kind].load(), kRankName[kind],
-                         h.nat_syrk_mflops[kind].load() * 1e-6);
-    static const char* const kSymmName[2] = {"SYMM", "HEMM"};
-    for (int kind = 0; kind < 2; ++kind)
-        if (h.emu_symm[kind].load() + h.nat_symm[kind].load())
-            std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu %s calls (%.3f TFLOP), native %llu %s calls through the hooked entry points (%.3f TFLOP)\n",
-                         h.emu_symm[kind].load(), kSymmName[kind], h.emu_symm_mflops[kind].load() * 1e-6, h.nat_symm[kind].load(), kSymmName[kind],
-                         h.nat_symm_mflops[kind].load() * 1e-6);
-    if (h.emu_trmm.load() + h.nat_trmm.load())
-        std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu TRMM calls (%.3f TFLOP), native %llu TRMM calls through the hooked entry points (%.3f TFLOP)\n",
-                     h.emu_trmm.load(), h.emu_trmm_mflops.load() * 1e-6, h.nat_trmm.load(), h.nat_trmm_mflops.load() * 1e-6);
-    if (h.emu_trsm.load() + h.nat_trsm.load())
-        std::fprintf(stderr, "[GEMMUL8 HOOK] stats: emulated %llu TRSM calls (%.3f TFLOP), native %llu TRSM calls through the hooked entry points (%.3f TFLOP)\n",
-                     h.emu_trsm.load(), h.emu_trsm_mflops.load() * 1e-6, h.nat_trsm.load(), h.nat_trsm_mflops.load() * 1e-6);
+                         n[0][0].load(), kRoutine[r].name, n[0][1].load() * 1e-6, n[1][0].load(), kRoutine[r].name, n[1][1].load() * 1e-6);
+    }
 }
 void count_call(bool emulated, const GemmCall& c) {
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
@@ -644,33 +671,52 @@ bool floor_model_declines(int dtype, double m, double n, double k, unsigned N, b
     const double tn = fm.n[0] + batch * (fm.n[1] * mn + fm.n[2] * mnk);
     return te > 0.95 * tn;
 }
-// quiet = a query (gemmul8_hook_would_emulate), not a call: no log line.  syrk = 1: a SYRK call, 2: a HERK call (m == n): a number is a floor on
-// n (n + 1) k, `auto` takes the GEMM model's decision for (n, n, k) -- native and emulated SYRK / HERK are both about half their GEMMs; no scan of
-// either has been fitted.  syrk = 3: a SYR2K call: a number is a floor on 2 n (n + 1) k; the caller passes 2 k, so that `auto` takes the GEMM model's
-// decision for (n, n, 2 k) -- no SYR2K scan has been fitted either.  syrk = 4: a HER2K call: a number is a floor on 8 n (n + 1) k (the routine's real
-// operations), `auto` takes the GEMM model's decision for (n, n, k), the one GEMM the call runs -- no HER2K scan has been fitted.
-bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch = 1.0, bool quiet = false, int syrk = 0) {
+// quiet = a query (gemmul8_hook_would_emulate), not a call: no log line
+bool below_floor(int dtype, double m, double n, double k, unsigned N, bool fast, int backend, double batch = 1.0, bool quiet = false) {
     const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
     if (!s || !*s) return false;  // the reference's behaviour: every selected call is emulated
     bool declined;
-    const bool automatic = (s[0] == 'a' || s[0] == 'A');
-    if (automatic) {
+    if (s[0] == 'a' || s[0] == 'A') {
         declined = floor_model_declines(dtype, m, n, k, N, fast, backend, batch);
     } else {
         const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
-        declined = f && (syrk == 4 ? 8.0 * n * (n + 1.0) * k : syrk ? n * (n + 1.0) * k : 2.0 * m * n * k) < (double)f;  // (SYR2K: k is 2 k here)
+        declined = f && 2.0 * m * n * k < (double)f;
     }
     if (declined && !quiet) {
-        static std::once_flag told[1 + kRankKinds];  // GEMM, SYRK, HERK, SYR2K, HER2K
-        std::call_once(told[syrk], [&] {
-            if (syrk)
-                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %c%s n = %.0f, k = %.0f (%u moduli) stays on the native routine -- calls below the "
-                                     "floor are NOT emulated%s (this message is printed once)\n", s, "SDCZ"[dtype], kRankName[syrk - 1], n, syrk == 3 ? 0.5 * k : k, N,
-                             syrk == 4 ? "; no HER2K scan has been fitted: a number is a floor on 8 n (n + 1) k, `auto` is the GEMM model's decision for (n, n, k)" : "");
+        static std::once_flag told;
+        std::call_once(told, [&] {
+            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cGEMM %.0f x %.0f x %.0f (batch %.0f, %u moduli%s) stays on the native routine -- "
+                                 "calls below the floor are NOT emulated (this message is printed once)\n",
+                         s, "SDCZ"[dtype], m, n, k, batch, N, backend == GEMMUL8_FP8 ? ", FP8 backend: cost x 1.75-2.1" : "");
+        });
+    }
+    return declined;
+}
+// the same for a Level-3 call on the INT8 backend (RoutineInfo::floor_flops, auto_min_order); the first call of each routine that is declined is logged
+bool level3_below_floor(const Level3Call& c, unsigned N, bool fast) {
+    const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
+    if (!s || !*s) return false;
+    const RoutineInfo& ri = kRoutine[c.routine];
+    const double m = (double)c.m, n = (double)c.n, k = (double)c.k, ka = c.side == HIPBLAS_SIDE_RIGHT ? n : m;
+    bool declined;
+    if (s[0] == 'a' || s[0] == 'A') {
+        declined = ri.auto_min_order ? ka < (double)ri.auto_min_order
+                   : ri.side         ? floor_model_declines(c.dtype, m, n, ka, N, fast, GEMMUL8_INT8, 1.0)
+                                     : floor_model_declines(c.dtype, n, n, ri.k_fold * k, N, fast, GEMMUL8_INT8, 1.0);
+    } else {
+        const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
+        declined = f && ri.floor_flops * c.flops() < (double)f;
+    }
+    if (declined) {
+        static std::once_flag told[kRoutines];
+        std::call_once(told[c.routine], [&] {
+            if (ri.side)
+                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %c%s m = %.0f, n = %.0f, order of A = %.0f (%u moduli) stays on the native routine -- calls "
+                                     "below the floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[c.dtype], ri.name, m, n, ka, N);
             else
-                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cGEMM %.0f x %.0f x %.0f (batch %.0f, %u moduli%s) stays on the native routine -- "
-                                     "calls below the floor are NOT emulated (this message is printed once)\n",
-                             s, "SDCZ"[dtype], m, n, k, batch, N, backend == GEMMUL8_FP8 ? ", FP8 backend: cost x 1.75-2.1" : "");
+                std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %c%s n = %.0f, k = %.0f (%u moduli) stays on the native routine -- calls below the "
+                                     "floor are NOT emulated%s (this message is printed once)\n", s, "SDCZ"[c.dtype], ri.name, n, k, N,
+                             c.routine == kHER2K ? "; no HER2K scan has been fitted: a number is a floor on 8 n (n + 1) k, `auto` is the GEMM model's decision for (n, n, k)" : "");
         });
     }
     return declined;
@@ -766,376 +812,133 @@ bool try_emulate(hipblasHandle_t handle, const GemmCall& c, hipblasStatus_t* sta
     return served;
 }
 
-// ---- hipblas{S,D,C,Z}syrk and hipblas{C,Z}herk (and the _64 twins): one triangle of alpha A A^T + beta C through gemmul8_syrk, of alpha A A^H + beta C
-// (real alpha, beta) through gemmul8_herk (no counterpart in the reference).  One body; herm selects the entry point, the operations that are taken
-// (N / T, N / C) and the name in the log lines.
-// Selection: the type's GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, k > 2^17, a moduli count outside
-// the type's range, GEMMUL8_NONFINITE=ieee (each said once per routine), a fill mode or operation other than upper / lower and N / T (HERK: N / C), a dimension an int cannot
-// hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: below_floor's SYRK / HERK form.  GEMMUL8_DIST and the skip-scaling switches do not apply.
-// hipblas{S,D,C,Z}syr2k (kind = kSYR2K; B != nullptr): one triangle of alpha (A B^T + B A^T) + beta C through gemmul8_syr2k -- the same selection, with
-// k <= 2^16 (the equivalent GEMM's inner dimension is 2 pad256(k)), that GEMM's workspace, and below_floor's SYR2K form.
-// hipblas{C,Z}her2k (kind = kHER2K; B != nullptr; complex alpha, real beta): one triangle of alpha A B^H + conj(alpha) B A^H + beta C through gemmul8_her2k --
-// the same selection with N / C, k <= 2^17, the workspace of the GEMM (n, n, k), and below_floor's HER2K form.
-bool try_syrk_impl(int kind, hipblasHandle_t handle, int dtype, int uplo, int trans, int n, int k, const void* alpha, const void* A, int lda, const void* B,
-                   int ldb, const void* beta, void* C, int ldc, hipblasStatus_t* status) {
-    const bool her2 = kind == kHER2K, herm = kind == kHERK || her2, two = kind == kSYR2K;
-    if (!(her2 ? (bool)abi().her2k : two ? (bool)abi().syr2k : herm ? (bool)abi().herk : (bool)abi().syrk)) return false;
-    const char* const name = kRankName[kind];
-    const int max_k = two ? kMaxK / 2 : kMaxK;
-    if ((uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) || (trans != HIPBLAS_OP_N && trans != (herm ? HIPBLAS_OP_C : HIPBLAS_OP_T)))
-        return false;
+// ---- the gate of the Level-3 routines (kRoutine).  Selection: the type's GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  The native routine takes: a
+// library without the entry point, a side / fill mode / operation / diag outside what the routine takes (RoutineInfo::ops; an enum value hipBLAS does not
+// define included), a moduli count outside the type's range, the FP8 backend, a k (rank-k) or an order of A (side) above RoutineInfo::limit,
+// GEMMUL8_NONFINITE=ieee -- the gemmul8_* entry points ignore the non-finite mode, a NaN or Inf operand would come back as finite numbers -- (each said once
+// per routine) and a call below GEMMUL8_MIN_FLOPS (level3_below_floor).  GEMMUL8_DIST and the skip-scaling switches do not apply.  The workspace -- that of
+// the GEMM the call amounts to (SYR2K: inner dimension 2 pad256(k)), gemmul8_trsm_work_size for TRSM -- grows through wC.
+// Returns true and sets *status when the call was served here (emulated, or failed), false -> the caller passes it through.  c has passed try_level3's screens.
+bool emulate_level3(hipblasHandle_t handle, const Level3Call& c, hipblasStatus_t* status) {
+    const RoutineInfo& ri = kRoutine[c.routine];
+    const Abi& abi_ = abi();
+    bool present = false;  // a library linked with this file may lack the entry point (OZ2_ABI)
+    switch (c.routine) {
+    case kSYRK: present = abi_.syrk; break;
+    case kHERK: present = abi_.herk; break;
+    case kSYR2K: present = abi_.syr2k; break;
+    case kHER2K: present = abi_.her2k; break;
+    case kSYMM: present = abi_.symm; break;
+    case kHEMM: present = abi_.hemm; break;
+    case kTRMM: present = abi_.trmm; break;
+    case kTRSM: present = abi_.trsm && abi_.trsm_work_size; break;
+    case kRoutines: break;
+    }
+    if (!present) return false;
+    if (c.uplo != HIPBLAS_FILL_MODE_UPPER && c.uplo != HIPBLAS_FILL_MODE_LOWER) return false;
+    if (ri.side && c.side != HIPBLAS_SIDE_LEFT && c.side != HIPBLAS_SIDE_RIGHT) return false;
+    const bool n_ = c.trans == HIPBLAS_OP_N, t_ = c.trans == HIPBLAS_OP_T, c_ = c.trans == HIPBLAS_OP_C;
+    switch (ri.ops) {
+    case kOpsNT: if (!n_ && !t_) return false; break;
+    case kOpsNC: if (!n_ && !c_) return false; break;
+    case kOpsNTC: if ((!n_ && !t_ && !c_) || (c.diag != HIPBLAS_DIAG_NON_UNIT && c.diag != HIPBLAS_DIAG_UNIT)) return false; break;
+    case kOpsNone: break;
+    }
+    const int dtype = c.dtype, m = (int)c.m, n = (int)c.n, k = (int)c.k, ka = c.side == HIPBLAS_SIDE_RIGHT ? n : m;
+    const int limited = ri.side ? ka : k;  // the dimension the limit is on
     Selection s;
     if (!selection_from_env(dtype, &s)) {
         if (s.N != 0) {
-            static std::once_flag told[kRankKinds];
-            std::call_once(told[kind], [&] {
+            static std::once_flag told[kRoutines];
+            std::call_once(told[c.routine], [&] {
                 std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %c%s calls use the native routine\n", kTypes[dtype].nmod, s.N,
-                             kTypes[dtype].max_moduli, "SDCZ"[dtype], name);
+                             kTypes[dtype].max_moduli, "SDCZ"[dtype], ri.name);
             });
         }
         return false;
     }
-    if (s.backend == GEMMUL8_FP8 || k > max_k) {
-        static std::once_flag told[kRankKinds][2];  // the backend, the k range: one notice each
-        std::call_once(told[kind][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for k <= %d only (GEMMUL8_BACKEND=%d, k=%d): using the native routine "
-                                 "for such calls\n", name, max_k, s.backend, k);
+    if (s.backend == GEMMUL8_FP8 || limited > ri.limit) {
+        static std::once_flag told[kRoutines][2];  // the backend, the size: one notice each
+        std::call_once(told[c.routine][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
+            if (ri.side)
+                std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for an A of order <= %d only (GEMMUL8_BACKEND=%d, order %d): using the native "
+                                     "routine for such calls\n", ri.name, ri.limit, s.backend, ka);
+            else
+                std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for k <= %d only (GEMMUL8_BACKEND=%d, k=%d): using the native routine "
+                                     "for such calls\n", ri.name, ri.limit, s.backend, k);
         });
         return false;
     }
-    if (nonfinite_ieee()) {  // gemmul8_syrk / herk / syr2k / her2k ignore the non-finite mode: a NaN or Inf operand would come back as finite numbers
-        static std::once_flag told[kRankKinds];
-        std::call_once(told[kind], [&] {
+    if (nonfinite_ieee()) {
+        static std::once_flag told[kRoutines];
+        std::call_once(told[c.routine], [&] {
             std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: %s has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
-                                 "for such calls\n", name);
+                                 "for such calls\n", ri.name);
         });
         return false;
     }
-    if (below_floor(dtype, (double)n, (double)n, (two ? 2.0 : 1.0) * (double)k, s.N, s.fast, s.backend, 1.0, false, kind + 1)) return false;
+    if (level3_below_floor(c, s.N, s.fast)) return false;
     LockedState l = lock_ordered(handle, nullptr);
     if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
-    const size_t kw = two ? 2 * (((size_t)k + 255) / 256 * 256) : (size_t)k;  // the inner dimension of the GEMM whose workspace the call needs
-    const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)n, (size_t)n, kw, s.N, 0, 0, nullptr, nullptr);
-    static const char* const what[kRankKinds] = {"workC (syrk)", "workC (herk)", "workC (syr2k)", "workC (her2k)"};
-    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, what[kind]); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
-    const int rc = (two || her2) ? (her2 ? abi().her2k : abi().syr2k)(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, B, (size_t)ldb, beta, C, (size_t)ldc,
-                                     s.N, s.fast, l.sp->wC.ptr, nullptr)
-                       : (herm ? abi().herk : abi().syrk)(l.stream, dtype, GEMMUL8_INT8, uplo, trans, (size_t)n, (size_t)k, alpha, A, (size_t)lda, beta, C,
-                                                          (size_t)ldc, s.N, s.fast, l.sp->wC.ptr, nullptr);
+    const bool cplx = kTypes[dtype].cplx;
+    const size_t sm = (size_t)m, sn = (size_t)n, sk = (size_t)k, lda = (size_t)c.lda, ldb = (size_t)c.ldb, ldc = (size_t)c.ldc;
+    const size_t need = c.routine == kTRSM ? abi_.trsm_work_size(cplx, GEMMUL8_INT8, c.side, sm, sn, s.N)
+                        : ri.side          ? abi_.work_size(cplx, GEMMUL8_INT8, sm, sn, (size_t)ka, s.N, 0, 0, nullptr, nullptr)
+                                           : abi_.work_size(cplx, GEMMUL8_INT8, sn, sn, ri.k_fold == 1 ? sk : ri.k_fold * ((sk + 255) / 256 * 256), s.N, 0, 0, nullptr, nullptr);
+    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, ri.tag); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
+    void* const work = l.sp->wC.ptr;
+    int rc = GEMMUL8_E_ARG;
+    switch (c.routine) {
+    case kSYRK:
+    case kHERK:
+        rc = (c.routine == kHERK ? abi_.herk : abi_.syrk)(l.stream, dtype, GEMMUL8_INT8, c.uplo, c.trans, sn, sk, c.alpha, c.A, lda, c.beta, c.C, ldc, s.N, s.fast, work, nullptr);
+        break;
+    case kSYR2K:
+    case kHER2K:
+        rc = (c.routine == kHER2K ? abi_.her2k : abi_.syr2k)(l.stream, dtype, GEMMUL8_INT8, c.uplo, c.trans, sn, sk, c.alpha, c.A, lda, c.B, ldb, c.beta, c.C, ldc, s.N, s.fast,
+                                                             work, nullptr);
+        break;
+    case kSYMM:
+    case kHEMM:
+        rc = (c.routine == kHEMM ? abi_.hemm : abi_.symm)(l.stream, dtype, GEMMUL8_INT8, c.side, c.uplo, sm, sn, c.alpha, c.A, lda, c.B, ldb, c.beta, c.C, ldc, s.N, s.fast, work,
+                                                          nullptr);
+        break;
+    case kTRMM:
+        rc = abi_.trmm(l.stream, dtype, GEMMUL8_INT8, c.side, c.uplo, c.trans, c.diag, sm, sn, c.alpha, c.A, lda, c.B, ldb, c.C, ldc, s.N, s.fast, work, nullptr);
+        break;
+    case kTRSM:
+        rc = abi_.trsm(l.stream, dtype, GEMMUL8_INT8, c.side, c.uplo, c.trans, c.diag, sm, sn, c.alpha, c.A, lda, c.C, ldc, s.N, s.fast, work, nullptr);
+        break;
+    case kRoutines: break;
+    }
     if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
-        static std::once_flag warned[kRankKinds];
-        std::call_once(warned[kind], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a %s call (status %d; type %d, n=%d k=%d): using the native routine for such calls\n", name,
-                         rc, dtype, n, k);
+        static std::once_flag warned[kRoutines];
+        std::call_once(warned[c.routine], [&] {
+            if (ri.side)
+                std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a %s call (status %d; type %d, m=%d n=%d): using the native routine for such calls\n", ri.name, rc,
+                             dtype, m, n);
+            else
+                std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a %s call (status %d; type %d, n=%d k=%d): using the native routine for such calls\n", ri.name, rc,
+                             dtype, n, k);
         });
         return false;
     }
     return *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR, true;
 }
-// counted front end; false = the native routine takes the call: also an empty product, a null pointer (the native routine reports it) or a
-// dimension an int cannot hold
-bool try_syrk(int kind, hipblasHandle_t handle, int dtype, int uplo, int trans, int64_t n, int64_t k, const void* alpha, const void* A, int64_t lda,
-              const void* B, int64_t ldb, const void* beta, void* C, int64_t ldc, hipblasStatus_t* status) {
+// counted front end (GEMMUL8_HOOK_STATS); false = the native routine takes the call: also, uncounted, a call inside a native pass-through, an empty call, a null
+// pointer (the native routine reports it) and a dimension an int cannot hold
+bool try_level3(hipblasHandle_t handle, const Level3Call& c, hipblasStatus_t* status) {
     if (tl_native_depth > 0) return false;
-    const int64_t lim = 2147483647;
-    if (n <= 0 || k <= 0 || !alpha || !beta || !A || !C || n > lim || k > lim || lda > lim || ldc > lim) return false;
-    if ((kind == kSYR2K || kind == kHER2K) && (!B || ldb > lim)) return false;
-    const bool served = try_syrk_impl(kind, handle, dtype, uplo, trans, (int)n, (int)k, alpha, A, (int)lda, B, (int)ldb, beta, C, (int)ldc, status);
+    const RoutineInfo& ri = kRoutine[c.routine];
+    const int64_t lim = 2147483647, other = ri.side ? c.m : c.k;
+    if (c.n <= 0 || other <= 0 || !c.alpha || !c.A || !c.C || (ri.beta && !c.beta) || (ri.B && !c.B)) return false;
+    if (c.n > lim || other > lim || c.lda > lim || c.ldb > lim || c.ldc > lim) return false;
+    const bool served = emulate_level3(handle, c, status);
     static const bool on = env_one("GEMMUL8_HOOK_STATS");
     if (on) {
-        HookStats& h = hook_stats();
-        const unsigned long long mf = (unsigned long long)((double)n * ((double)n + 1.0) * (double)k * (dtype >= 2 ? 4.0 : 1.0) * (kind == kSYR2K || kind == kHER2K ? 2.0 : 1.0) * 1e-6);
-        (served ? h.emu_syrk : h.nat_syrk)[kind].fetch_add(1, std::memory_order_relaxed);
-        (served ? h.emu_syrk_mflops : h.nat_syrk_mflops)[kind].fetch_add(mf, std::memory_order_relaxed);
-    }
-    return served;
-}
-
-// ---- hipblas{S,D,C,Z}symm and hipblas{C,Z}hemm (and the _64 twins): C = alpha A B + beta C / alpha B A + beta C with a symmetric / Hermitian A of which one
-// triangle is stored, through gemmul8_symm / gemmul8_hemm (no counterpart in the reference).  ka = the order of A (m for side = left, n for right).
-// Selection: the type's GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, ka > 2^17, a moduli count outside the
-// type's range, GEMMUL8_NONFINITE=ieee (each said once per routine), a side or fill mode other than left / right and upper / lower, a dimension an int
-// cannot hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: a number is a floor on 2 m n ka, `auto` takes the GEMM model's decision for
-// (m, n, ka).  GEMMUL8_DIST and the skip-scaling switches do not apply.  The workspace (the equivalent GEMM's) grows through wC, as for SYRK.
-enum { kSYMM = 0, kHEMM = 1 };
-bool symm_below_floor(int kind, int dtype, double m, double n, double ka, unsigned N, bool fast) {
-    const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
-    if (!s || !*s) return false;
-    bool declined;
-    if (s[0] == 'a' || s[0] == 'A') {
-        declined = floor_model_declines(dtype, m, n, ka, N, fast, GEMMUL8_INT8, 1.0);
-    } else {
-        const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
-        declined = f && 2.0 * m * n * ka < (double)f;
-    }
-    if (declined) {
-        static std::once_flag told[2];
-        std::call_once(told[kind], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %c%s m = %.0f, n = %.0f, order of A = %.0f (%u moduli) stays on the native routine -- calls "
-                                 "below the floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], kind == kHEMM ? "HEMM" : "SYMM", m, n, ka, N);
-        });
-    }
-    return declined;
-}
-bool try_symm_impl(int kind, hipblasHandle_t handle, int dtype, int side, int uplo, int m, int n, const void* alpha, const void* A, int lda, const void* B,
-                   int ldb, const void* beta, void* C, int ldc, hipblasStatus_t* status) {
-    if (!(kind == kHEMM ? (bool)abi().hemm : (bool)abi().symm)) return false;
-    const char* const name = kind == kHEMM ? "HEMM" : "SYMM";
-    if ((side != HIPBLAS_SIDE_LEFT && side != HIPBLAS_SIDE_RIGHT) || (uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER)) return false;
-    const int ka = side == HIPBLAS_SIDE_LEFT ? m : n;
-    Selection s;
-    if (!selection_from_env(dtype, &s)) {
-        if (s.N != 0) {
-            static std::once_flag told[2];
-            std::call_once(told[kind], [&] {
-                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %c%s calls use the native routine\n", kTypes[dtype].nmod, s.N,
-                             kTypes[dtype].max_moduli, "SDCZ"[dtype], name);
-            });
-        }
-        return false;
-    }
-    if (s.backend == GEMMUL8_FP8 || ka > kMaxK) {
-        static std::once_flag told[2][2];  // the backend, the order of A: one notice each
-        std::call_once(told[kind][s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] %s is emulated on the INT8 backend for an A of order <= %d only (GEMMUL8_BACKEND=%d, order %d): using the native "
-                                 "routine for such calls\n", name, kMaxK, s.backend, ka);
-        });
-        return false;
-    }
-    if (nonfinite_ieee()) {  // gemmul8_symm / hemm ignore the non-finite mode: a NaN or Inf operand would come back as finite numbers
-        static std::once_flag told[2];
-        std::call_once(told[kind], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: %s has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
-                                 "for such calls\n", name);
-        });
-        return false;
-    }
-    if (symm_below_floor(kind, dtype, (double)m, (double)n, (double)ka, s.N, s.fast)) return false;
-    LockedState l = lock_ordered(handle, nullptr);
-    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
-    const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)m, (size_t)n, (size_t)ka, s.N, 0, 0, nullptr, nullptr);
-    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, kind == kHEMM ? "workC (hemm)" : "workC (symm)"); st != HIPBLAS_STATUS_SUCCESS)
-        return *status = st, true;
-    const int rc = (kind == kHEMM ? abi().hemm : abi().symm)(l.stream, dtype, GEMMUL8_INT8, side, uplo, (size_t)m, (size_t)n, alpha, A, (size_t)lda, B, (size_t)ldb,
-                                                             beta, C, (size_t)ldc, s.N, s.fast, l.sp->wC.ptr, nullptr);
-    if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
-        static std::once_flag warned[2];
-        std::call_once(warned[kind], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a %s call (status %d; type %d, m=%d n=%d): using the native routine for such calls\n", name, rc,
-                         dtype, m, n);
-        });
-        return false;
-    }
-    return *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR, true;
-}
-// counted front end; false = the native routine takes the call: also an empty product, a null pointer (the native routine reports it) or a
-// dimension an int cannot hold
-bool try_symm(int kind, hipblasHandle_t handle, int dtype, int side, int uplo, int64_t m, int64_t n, const void* alpha, const void* A, int64_t lda,
-              const void* B, int64_t ldb, const void* beta, void* C, int64_t ldc, hipblasStatus_t* status) {
-    if (tl_native_depth > 0) return false;
-    const int64_t lim = 2147483647;
-    if (m <= 0 || n <= 0 || !alpha || !beta || !A || !B || !C || m > lim || n > lim || lda > lim || ldb > lim || ldc > lim) return false;
-    const bool served = try_symm_impl(kind, handle, dtype, side, uplo, (int)m, (int)n, alpha, A, (int)lda, B, (int)ldb, beta, C, (int)ldc, status);
-    static const bool on = env_one("GEMMUL8_HOOK_STATS");
-    if (on) {
-        HookStats& h = hook_stats();
-        const double ka = side == HIPBLAS_SIDE_RIGHT ? (double)n : (double)m;
-        const unsigned long long mf = (unsigned long long)(2.0 * (double)m * (double)n * ka * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
-        (served ? h.emu_symm : h.nat_symm)[kind].fetch_add(1, std::memory_order_relaxed);
-        (served ? h.emu_symm_mflops : h.nat_symm_mflops)[kind].fetch_add(mf, std::memory_order_relaxed);
-    }
-    return served;
-}
-
-// ---- hipblas{S,D,C,Z}trmm (and the _64 twins; ROCm 7's out-of-place signature): C = alpha op(A) B / alpha B op(A) with a triangular A, through
-// gemmul8_trmm (no counterpart in the reference).  ka = the order of A (m for side = left, n for right).  Selection as for SYMM: the type's
-// GEMMUL8_NUM_MOD_* / GEMMUL8_FASTMODE_*, GEMMUL8_BACKEND.  Native routine: the FP8 backend, ka > 2^17, a moduli count outside the type's range,
-// GEMMUL8_NONFINITE=ieee (each said once), an enum value hipBLAS does not define, a dimension an int cannot hold, a library without the entry point.
-// GEMMUL8_MIN_FLOPS: a number is a floor on m n ka, the routine's own flop count; `auto` takes the GEMM model's decision for (m, n, ka) -- conservative, the
-// routine does less work than that GEMM.  The workspace (the equivalent GEMM's) grows through wC, as for SYMM.  C == B (in place) is gemmul8_trmm's contract.
-bool trmm_below_floor(int dtype, double m, double n, double ka, unsigned N, bool fast) {
-    const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
-    if (!s || !*s) return false;
-    bool declined;
-    if (s[0] == 'a' || s[0] == 'A') {
-        declined = floor_model_declines(dtype, m, n, ka, N, fast, GEMMUL8_INT8, 1.0);
-    } else {
-        const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
-        declined = f && m * n * ka < (double)f;
-    }
-    if (declined) {
-        static std::once_flag told;
-        std::call_once(told, [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cTRMM m = %.0f, n = %.0f, order of A = %.0f (%u moduli) stays on the native routine -- calls "
-                                 "below the floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], m, n, ka, N);
-        });
-    }
-    return declined;
-}
-bool try_trmm_impl(hipblasHandle_t handle, int dtype, int side, int uplo, int transA, int diag, int m, int n, const void* alpha, const void* A, int lda,
-                   const void* B, int ldb, void* C, int ldc, hipblasStatus_t* status) {
-    if (!abi().trmm) return false;
-    if ((side != HIPBLAS_SIDE_LEFT && side != HIPBLAS_SIDE_RIGHT) || (uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) ||
-        (transA != HIPBLAS_OP_N && transA != HIPBLAS_OP_T && transA != HIPBLAS_OP_C) || (diag != HIPBLAS_DIAG_NON_UNIT && diag != HIPBLAS_DIAG_UNIT))
-        return false;
-    const int ka = side == HIPBLAS_SIDE_LEFT ? m : n;
-    Selection s;
-    if (!selection_from_env(dtype, &s)) {
-        if (s.N != 0) {
-            static std::once_flag told;
-            std::call_once(told, [&] {
-                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %cTRMM calls use the native routine\n", kTypes[dtype].nmod, s.N, kTypes[dtype].max_moduli,
-                             "SDCZ"[dtype]);
-            });
-        }
-        return false;
-    }
-    if (s.backend == GEMMUL8_FP8 || ka > kMaxK) {
-        static std::once_flag told[2];  // the backend, the order of A: one notice each
-        std::call_once(told[s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] TRMM is emulated on the INT8 backend for an A of order <= %d only (GEMMUL8_BACKEND=%d, order %d): using the native "
-                                 "routine for such calls\n", kMaxK, s.backend, ka);
-        });
-        return false;
-    }
-    if (nonfinite_ieee()) {  // gemmul8_trmm ignores the non-finite mode: a NaN or Inf operand would come back as finite numbers
-        static std::once_flag told;
-        std::call_once(told, [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: TRMM has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
-                                 "for such calls\n");
-        });
-        return false;
-    }
-    if (trmm_below_floor(dtype, (double)m, (double)n, (double)ka, s.N, s.fast)) return false;
-    LockedState l = lock_ordered(handle, nullptr);
-    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
-    const size_t need = abi().work_size(kTypes[dtype].cplx, GEMMUL8_INT8, (size_t)m, (size_t)n, (size_t)ka, s.N, 0, 0, nullptr, nullptr);
-    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, "workC (trmm)"); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
-    const int rc = abi().trmm(l.stream, dtype, GEMMUL8_INT8, side, uplo, transA, diag, (size_t)m, (size_t)n, alpha, A, (size_t)lda, B, (size_t)ldb, C, (size_t)ldc,
-                              s.N, s.fast, l.sp->wC.ptr, nullptr);
-    if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
-        static std::once_flag warned;
-        std::call_once(warned, [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a TRMM call (status %d; type %d, m=%d n=%d): using the native routine for such calls\n", rc, dtype, m,
-                         n);
-        });
-        return false;
-    }
-    return *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR, true;
-}
-// counted front end; false = the native routine takes the call: also an empty product, a null pointer (the native routine reports it) or a
-// dimension an int cannot hold
-bool try_trmm(hipblasHandle_t handle, int dtype, int side, int uplo, int transA, int diag, int64_t m, int64_t n, const void* alpha, const void* A, int64_t lda,
-              const void* B, int64_t ldb, void* C, int64_t ldc, hipblasStatus_t* status) {
-    if (tl_native_depth > 0) return false;
-    const int64_t lim = 2147483647;
-    if (m <= 0 || n <= 0 || !alpha || !A || !B || !C || m > lim || n > lim || lda > lim || ldb > lim || ldc > lim) return false;
-    const bool served = try_trmm_impl(handle, dtype, side, uplo, transA, diag, (int)m, (int)n, alpha, A, (int)lda, B, (int)ldb, C, (int)ldc, status);
-    static const bool on = env_one("GEMMUL8_HOOK_STATS");
-    if (on) {
-        HookStats& h = hook_stats();
-        const double ka = side == HIPBLAS_SIDE_RIGHT ? (double)n : (double)m;
-        const unsigned long long mf = (unsigned long long)((double)m * (double)n * ka * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
-        (served ? h.emu_trmm : h.nat_trmm).fetch_add(1, std::memory_order_relaxed);
-        (served ? h.emu_trmm_mflops : h.nat_trmm_mflops).fetch_add(mf, std::memory_order_relaxed);
-    }
-    return served;
-}
-
-// ---- hipblas{S,D,C,Z}trsm (and the _64 twins): op(A) X = alpha B / X op(A) = alpha B, X over B, through gemmul8_trsm (no counterpart in the reference).
-// Selection and the ways to the native routine as for TRMM: the FP8 backend, ka > 2^17, a moduli count outside the type's range, GEMMUL8_NONFINITE=ieee (each
-// said once), an enum value hipBLAS does not define, a dimension an int cannot hold, a library without the entry point.  GEMMUL8_MIN_FLOPS: a number is a
-// floor on m n ka; `auto` declines below the order kTrsmAutoMinOrder.  The workspace (gemmul8_trsm_work_size) grows through wC.
-//
-// kTrsmAutoMinOrder: the smallest measured order of A from which the emulated routine beats the native one at n = ka in float64 accurate mode
-// (profiles/trsm_ab.json, tools/trsm_ab.py; INTEGRATION.md "TRSM" prints the table): DTRSM left at 14 moduli loses at 8192 x 8192 (25.1 against 19.4 ms) and
-// wins at 16384 x 16384 (88.6 against 108.1 ms).  The rule asks for the order only: it also declines the right-side 8192 x 8192 row, which the emulation wins.
-constexpr int kTrsmAutoMinOrder = 16384;
-bool trsm_below_floor(int dtype, double m, double n, double ka, unsigned N) {
-    const char* s = std::getenv("GEMMUL8_MIN_FLOPS");
-    if (!s || !*s) return false;
-    bool declined;
-    if (s[0] == 'a' || s[0] == 'A') {
-        declined = ka < (double)kTrsmAutoMinOrder;
-    } else {
-        const unsigned long long f = env_u64("GEMMUL8_MIN_FLOPS", 0);
-        declined = f && m * n * ka < (double)f;
-    }
-    if (declined) {
-        static std::once_flag told;
-        std::call_once(told, [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_MIN_FLOPS=%s: a %cTRSM m = %.0f, n = %.0f, order of A = %.0f (%u moduli) stays on the native routine -- calls "
-                                 "below the floor are NOT emulated (this message is printed once)\n", s, "SDCZ"[dtype], m, n, ka, N);
-        });
-    }
-    return declined;
-}
-bool try_trsm_impl(hipblasHandle_t handle, int dtype, int side, int uplo, int transA, int diag, int m, int n, const void* alpha, const void* A, int lda, void* B,
-                   int ldb, hipblasStatus_t* status) {
-    if (!abi().trsm || !abi().trsm_work_size) return false;
-    if ((side != HIPBLAS_SIDE_LEFT && side != HIPBLAS_SIDE_RIGHT) || (uplo != HIPBLAS_FILL_MODE_UPPER && uplo != HIPBLAS_FILL_MODE_LOWER) ||
-        (transA != HIPBLAS_OP_N && transA != HIPBLAS_OP_T && transA != HIPBLAS_OP_C) || (diag != HIPBLAS_DIAG_NON_UNIT && diag != HIPBLAS_DIAG_UNIT))
-        return false;
-    const int ka = side == HIPBLAS_SIDE_LEFT ? m : n;
-    Selection s;
-    if (!selection_from_env(dtype, &s)) {
-        if (s.N != 0) {
-            static std::once_flag told;
-            std::call_once(told, [&] {
-                std::fprintf(stderr, "[GEMMUL8 HOOK] %s=%u is outside 2..%u: %cTRSM calls use the native routine\n", kTypes[dtype].nmod, s.N, kTypes[dtype].max_moduli,
-                             "SDCZ"[dtype]);
-            });
-        }
-        return false;
-    }
-    if (s.backend == GEMMUL8_FP8 || ka > kMaxK) {
-        static std::once_flag told[2];  // the backend, the order of A: one notice each
-        std::call_once(told[s.backend == GEMMUL8_FP8 ? 0 : 1], [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] TRSM is emulated on the INT8 backend for an A of order <= %d only (GEMMUL8_BACKEND=%d, order %d): using the native "
-                                 "routine for such calls\n", kMaxK, s.backend, ka);
-        });
-        return false;
-    }
-    if (nonfinite_ieee()) {  // gemmul8_trsm ignores the non-finite mode: its GEMM updates would turn a NaN or Inf operand into finite numbers
-        static std::once_flag told;
-        std::call_once(told, [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] GEMMUL8_NONFINITE=ieee: TRSM has no NaN / Inf propagation mode and is NOT emulated: using the native routine "
-                                 "for such calls\n");
-        });
-        return false;
-    }
-    if (trsm_below_floor(dtype, (double)m, (double)n, (double)ka, s.N)) return false;
-    LockedState l = lock_ordered(handle, nullptr);
-    if (l.st != HIPBLAS_STATUS_SUCCESS) return *status = l.st, true;
-    const size_t need = abi().trsm_work_size(kTypes[dtype].cplx, GEMMUL8_INT8, side, (size_t)m, (size_t)n, s.N);
-    if (const hipblasStatus_t st = grow(l.sp->wC, std::max(need, g_maxC), l.stream, "workC (trsm)"); st != HIPBLAS_STATUS_SUCCESS) return *status = st, true;
-    const int rc = abi().trsm(l.stream, dtype, GEMMUL8_INT8, side, uplo, transA, diag, (size_t)m, (size_t)n, alpha, A, (size_t)lda, B, (size_t)ldb, s.N, s.fast,
-                              l.sp->wC.ptr, nullptr);
-    if (rc < 0) {  // declined before anything was written: the native routine takes the call (see try_emulate_impl)
-        static std::once_flag warned;
-        std::call_once(warned, [&] {
-            std::fprintf(stderr, "[GEMMUL8 HOOK] emulation declined a TRSM call (status %d; type %d, m=%d n=%d): using the native routine for such calls\n", rc, dtype, m,
-                         n);
-        });
-        return false;
-    }
-    return *status = rc == 0 ? HIPBLAS_STATUS_SUCCESS : HIPBLAS_STATUS_INTERNAL_ERROR, true;
-}
-// counted front end; false = the native routine takes the call: also an empty call, a null pointer (the native routine reports it) or a dimension an int
-// cannot hold
-bool try_trsm(hipblasHandle_t handle, int dtype, int side, int uplo, int transA, int diag, int64_t m, int64_t n, const void* alpha, const void* A, int64_t lda,
-              void* B, int64_t ldb, hipblasStatus_t* status) {
-    if (tl_native_depth > 0) return false;
-    const int64_t lim = 2147483647;
-    if (m <= 0 || n <= 0 || !alpha || !A || !B || m > lim || n > lim || lda > lim || ldb > lim) return false;
-    const bool served = try_trsm_impl(handle, dtype, side, uplo, transA, diag, (int)m, (int)n, alpha, A, (int)lda, B, (int)ldb, status);
-    static const bool on = env_one("GEMMUL8_HOOK_STATS");
-    if (on) {
-        HookStats& h = hook_stats();
-        const double ka = side == HIPBLAS_SIDE_RIGHT ? (double)n : (double)m;
-        const unsigned long long mf = (unsigned long long)((double)m * (double)n * ka * (dtype >= 2 ? 4.0 : 1.0) * 1e-6);
-        (served ? h.emu_trsm : h.nat_trsm).fetch_add(1, std::memory_order_relaxed);
-        (served ? h.emu_trsm_mflops : h.nat_trsm_mflops).fetch_add(mf, std::memory_order_relaxed);
+        auto& n = hook_stats().level3[c.routine][served ? 0 : 1];
+        n[0].fetch_add(1, std::memory_order_relaxed);
+        n[1].fetch_add((unsigned long long)(ri.stats_flops * c.flops() * (c.dtype >= 2 ? 4.0 : 1.0) * 1e-6), std::memory_order_relaxed);
     }
     return served;
 }
@@ -1684,14 +1487,18 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
                          I lda, const T* beta, T* C, I ldc) {                                                                           \
         hipblasStatus_t st;                                                                                                             \
-        if (try_syrk(kSYRK, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, nullptr, 0, beta, C, ldc, &st)) return st;       \
+        const Level3Call c{.routine = kSYRK, .dtype = CODE, .uplo = (int)uplo, .trans = (int)transA, .n = n, .k = k, .alpha = alpha, .A = A, .lda = lda, \
+                           .beta = beta, .C = C, .ldc = ldc};                                                                           \
+        if (try_level3(handle, c, &st)) return st;                                                                                      \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, beta, C, ldc);                      \
     }
 #define OZ2_SYR2K_HOOK(NAME, T, I, CODE)                                                                                                \
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
                          I lda, const T* B, I ldb, const T* beta, T* C, I ldc) {                                                        \
         hipblasStatus_t st;                                                                                                             \
-        if (try_syrk(kSYR2K, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;          \
+        const Level3Call c{.routine = kSYR2K, .dtype = CODE, .uplo = (int)uplo, .trans = (int)transA, .n = n, .k = k, .alpha = alpha, .A = A, .lda = lda, \
+                           .B = B, .ldb = ldb, .beta = beta, .C = C, .ldc = ldc};                                                       \
+        if (try_level3(handle, c, &st)) return st;                                                                                      \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc);              \
     }
 // hipblas{S,D,C,Z}symm (KIND = kSYMM) and hipblas{C,Z}hemm (kHEMM): one signature
@@ -1699,7 +1506,9 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasSideMode_t side, hipblasFillMode_t uplo, I m, I n, const T* alpha, const T* A,  \
                          I lda, const T* B, I ldb, const T* beta, T* C, I ldc) {                                                        \
         hipblasStatus_t st;                                                                                                             \
-        if (try_symm(KIND, handle, CODE, (int)side, (int)uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;              \
+        const Level3Call c{.routine = KIND, .dtype = CODE, .side = (int)side, .uplo = (int)uplo, .m = m, .n = n, .alpha = alpha, .A = A, .lda = lda, \
+                           .B = B, .ldb = ldb, .beta = beta, .C = C, .ldc = ldc};                                                       \
+        if (try_level3(handle, c, &st)) return st;                                                                                      \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, m, n, alpha, A, lda, B, ldb, beta, C, ldc);                \
     }
 // hipblas{S,D,C,Z}trmm: ROCm 7's out-of-place signature (C may be B)
@@ -1707,15 +1516,19 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasSideMode_t side, hipblasFillMode_t uplo, hipblasOperation_t transA,             \
                          hipblasDiagType_t diag, I m, I n, const T* alpha, const T* A, I lda, const T* B, I ldb, T* C, I ldc) {         \
         hipblasStatus_t st;                                                                                                             \
-        if (try_trmm(handle, CODE, (int)side, (int)uplo, (int)transA, (int)diag, m, n, alpha, A, lda, B, ldb, C, ldc, &st)) return st;  \
+        const Level3Call c{.routine = kTRMM, .dtype = CODE, .side = (int)side, .uplo = (int)uplo, .trans = (int)transA, .diag = (int)diag, .m = m, .n = n, \
+                           .alpha = alpha, .A = A, .lda = lda, .B = B, .ldb = ldb, .C = C, .ldc = ldc};                                 \
+        if (try_level3(handle, c, &st)) return st;                                                                                      \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, transA, diag, m, n, alpha, A, lda, B, ldb, C, ldc);        \
     }
-// hipblas{S,D,C,Z}trsm: in place on B
+// hipblas{S,D,C,Z}trsm: in place on B, the matrix the call writes (Level3Call::C)
 #define OZ2_TRSM_HOOK(NAME, T, I, CODE)                                                                                                 \
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasSideMode_t side, hipblasFillMode_t uplo, hipblasOperation_t transA,             \
                          hipblasDiagType_t diag, I m, I n, const T* alpha, const T* A, I lda, T* B, I ldb) {                            \
         hipblasStatus_t st;                                                                                                             \
-        if (try_trsm(handle, CODE, (int)side, (int)uplo, (int)transA, (int)diag, m, n, alpha, A, lda, B, ldb, &st)) return st;          \
+        const Level3Call c{.routine = kTRSM, .dtype = CODE, .side = (int)side, .uplo = (int)uplo, .trans = (int)transA, .diag = (int)diag, .m = m, .n = n, \
+                           .alpha = alpha, .A = A, .lda = lda, .C = B, .ldc = ldb};                                                     \
+        if (try_level3(handle, c, &st)) return st;                                                                                      \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, side, uplo, transA, diag, m, n, alpha, A, lda, B, ldb);                \
     }
 // hipblas{C,Z}her2k: a complex alpha, R = the real type of beta
@@ -1723,7 +1536,9 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const T* alpha, const T* A, \
                          I lda, const T* B, I ldb, const R* beta, T* C, I ldc) {                                                        \
         hipblasStatus_t st;                                                                                                             \
-        if (try_syrk(kHER2K, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc, &st)) return st;          \
+        const Level3Call c{.routine = kHER2K, .dtype = CODE, .uplo = (int)uplo, .trans = (int)transA, .n = n, .k = k, .alpha = alpha, .A = A, .lda = lda, \
+                           .B = B, .ldb = ldb, .beta = beta, .C = C, .ldc = ldc};                                                       \
+        if (try_level3(handle, c, &st)) return st;                                                                                      \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, B, ldb, beta, C, ldc);              \
     }
 // hipblas{C,Z}herk: R = the real type of alpha and beta
@@ -1731,7 +1546,9 @@ hipblasStatus_t hipblasDestroy(hipblasHandle_t handle) {
     hipblasStatus_t NAME(hipblasHandle_t handle, hipblasFillMode_t uplo, hipblasOperation_t transA, I n, I k, const R* alpha, const T* A, \
                          I lda, const R* beta, T* C, I ldc) {                                                                           \
         hipblasStatus_t st;                                                                                                             \
-        if (try_syrk(kHERK, handle, CODE, (int)uplo, (int)transA, n, k, alpha, A, lda, nullptr, 0, beta, C, ldc, &st)) return st;       \
+        const Level3Call c{.routine = kHERK, .dtype = CODE, .uplo = (int)uplo, .trans = (int)transA, .n = n, .k = k, .alpha = alpha, .A = A, .lda = lda, \
+                           .beta = beta, .C = C, .ldc = ldc};                                                                           \
+        if (try_level3(handle, c, &st)) return st;                                                                                      \
         OZ2_NATIVE(NAME, HIPBLAS_STATUS_NOT_INITIALIZED, handle, uplo, transA, n, k, alpha, A, lda, beta, C, ldc);                      \
     }
 // one stamp per type; Z / ZZ: the substitution indices of the mangled names, which differ between the real and the complex forms
